@@ -17,8 +17,13 @@ N > 1: one process per GPU (torch.distributed, backend nccl = RCCL over xGMI).
   --scaling weak (BASELINE configs[4] shape): --scenes-per-gpu scenes per GPU, partitioned BY SCENE (the collated batch graph
       is block diagonal, threedfront_dataset.py:698-701), so no rank needs another rank's codes: no data-path collective at
       all; value = total scenes x steps / max-over-ranks time (scene-steps/s).
-At N = 1 the line also carries the BASELINE configs[1] (layout only) and configs[2] (16-node full step) results as
-``sub_records``.
+A plain run sets up, warms up, times exactly K steps once and prints the headline line (``metric``, ``value``, ``unit``,
+``higher_is_better``, ``dtype``, ``ms_per_step`` = wall milliseconds of one timed step).  Everything else it used to measure moves
+behind ``--full``: the median of ``--reps`` (5) repetitions, the per-loop replays, the dominant-kernel roofline, the other sharding
+mode (N > 1), and at N = 1 the BASELINE configs[1] (layout only) / configs[2] (16-node full step) ``sub_records``, the fp32 / fp32x
+route records and the CPU oracle baseline.
+``--dump-outputs DIR`` writes what the timed path computed in its last step (the final layout boxes and shape latents, float32)
+as DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -309,6 +314,25 @@ def configs4_record(dev, use_graph, scenes=8, O=32, n=5):
     return rec
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy in float32.  An array beyond its share of the 64 MB limit keeps a fixed,
+    seeded sample of its rows (sorted row indices: the same for every run of the same shape)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        x = t.detach().float().cpu().contiguous()
+        row = 4 * (x[0].numel() if x.dim() > 0 and x.shape[0] else 0)
+        if row and 4 * x.numel() > share:
+            keep = max(1, share // row)
+            idx = torch.randperm(x.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            x = x[idx]
+        np.save(os.path.join(path, name + '.npy'), x.numpy())
+
+
 def cpu_baseline_shape(df, uc, triples, O_sample, timed=2):
     """SURVEY 8(d): 1 warm-up + ``timed`` DDIM steps of the CPU oracle on the first O_sample objects (cost is linear in objects);
     returns seconds per step."""
@@ -417,7 +441,13 @@ def main():
     ap.add_argument('--fuse-loops', type=int, default=-1,
                     help='1: one hipGraph per full step with the layout step as a parallel branch of the shape step; 0: two streams; '
                          '-1: the default of this build')
-    ap.add_argument('--reps', type=int, default=5, help='repetitions of the timed K-step region (value = the median repetition)')
+    ap.add_argument('--reps', type=int, default=None,
+                    help='repetitions of the timed K-step region (value = the median repetition); default 1, 5 with --full')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure: 5 repetitions, per-loop replays, dominant-kernel roofline, other '
+                         'sharding mode, sub-records, fp32 / fp32x routes and the CPU baseline (off by default)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the arrays the timed path computed in its last step as DIR/<name>.npy (float32)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-alt-mode', action='store_true', help='N > 1: skip the record of the other sharding mode (other_sharding_mode)')
     ap.add_argument('--no-graph', action='store_true')
@@ -518,7 +548,8 @@ def main():
         from echoscene_amd.plan import combine_plans
         fused = combine_plans(dev, ss['plan'], st['plan'])
         st['step'].zero_()
-        fused.sample(ss['step'], 0, 2, use_graph=use_graph)          # capture outside the timed region
+        # capture outside the timed region, then the rest of the W warm-up steps on the timed path itself
+        fused.sample(ss['step'], 0, min(max(a.warmup, 2), sden.S), use_graph=use_graph)
         st['step'].zero_()
         torch.cuda.synchronize()
     # The two loops are independent given the setup (the reference runs them back to back); they are enqueued on
@@ -528,16 +559,28 @@ def main():
         ss['x'].copy_(xall[ss.get('lo', 0):ss.get('hi', O_all)])
         torch.cuda.synchronize()
     s_lay, s_shp = torch.cuda.Stream(), torch.cuda.Stream()
+    state_gen = torch.Generator(device=dev)
 
     def reset_state():
         """fresh noise states before every repetition (outside the timed bracket): a loop restarted at iteration 0 on the previous
-        repetition's RESULT treats a clean sample as noise, and on random weights a few such restarts overflow"""
+        repetition's RESULT treats a clean sample as noise, and on random weights a few such restarts overflow.  Seeded: every
+        repetition, and every run with the same arguments, starts from the same states (--dump-outputs compares builds)."""
         if a.check:
             return                               # (--check seeds the latents itself, one repetition)
-        st['noise'].normal_()
+        state_gen.manual_seed(1000 + rank)
+        st['noise'].normal_(generator=state_gen)
         st['x'].copy_(st['noise'][0])
+        st['step'].zero_()                       # (the fused loops advance the layout counter without resetting it)
         if full:
-            ss['x'].normal_()
+            ss['x'].normal_(generator=state_gen)
+
+    def fused_layout_wrap(lay_done, n):
+        """the fused plans advance the layout step counter on their own: restart it before it would run past the T-step schedule
+        (as the unfused loop does every den.T steps); returns the counter's position after the next n steps"""
+        if lay_done + n > den.T:
+            st['step'].zero_()
+            lay_done = 0
+        return lay_done + n
 
     def timed_region():
         """EXACTLY a.steps steps, bracketed by a barrier + device synchronisation on both sides; returns (wall s, layout-loop ms,
@@ -552,9 +595,10 @@ def main():
         if fused is not None:
             with torch.cuda.stream(s_shp):
                 ev[0].record(); ev[2].record()
-                done = 0
+                done = lay_done = 0
                 while done < a.steps:
                     n = min(a.steps - done, sden.S)
+                    lay_done = fused_layout_wrap(lay_done, n)
                     fused.sample(ss['step'], 0, n, use_graph=use_graph)
                     done += n
                 ev[1].record(); ev[3].record()
@@ -569,8 +613,11 @@ def main():
         with torch.cuda.stream(s_shp):
             ev[2].record() if fused is None else None
             done = a.steps if fused is not None else 0
+            lay_done = 0
             while full and done < a.steps:          # the DDIM loop is 100 iterations long
                 n = min(a.steps - done, sden.S)
+                if fused_sharded:
+                    lay_done = fused_layout_wrap(lay_done, n)
                 if sh_world == 1:
                     ss['plan'].sample(ss['step'], 0, n, use_graph=use_graph)
                 else:                               # per-step echo all-gather over RCCL (parallel.sharded_ddim_loop)
@@ -590,7 +637,7 @@ def main():
 
     # The K-step region is timed a.reps times (each repetition with its own barrier / synchronise bracket); `value` is the MEDIAN
     # repetition, min / max go into the line next to it (boxes and runs differ by a few per cent: VERDICT r3 #5).
-    reps = 1 if a.check else max(1, a.reps)
+    reps = 1 if a.check else max(1, a.reps if a.reps is not None else (5 if a.full else 1))
     regions = [timed_region() for _ in range(reps)]
     walls = sorted(r[0] for r in regions)
     wall = walls[len(walls) // 2] if len(walls) % 2 else 0.5 * (walls[len(walls) // 2 - 1] + walls[len(walls) // 2])
@@ -606,8 +653,20 @@ def main():
             z = torch.cat(parts, 0)
         check = {'latents_crc32': zlib.crc32(z.numpy().tobytes()), 'objects': int(z.shape[0]),
                  'abs_sum': float(z.double().abs().sum())}
+    if a.dump_outputs:                          # (likewise: the states the last timed step left)
+        outs = {'layout_boxes': st['x']}
+        if full:
+            outs['shape_latents'] = ss['x']
+        outs = {k: v.detach().float().cpu().contiguous() for k, v in outs.items()}
+        for k in list(outs):
+            if dist is not None and (weak or k == 'shape_latents'):      # (strong: the layout state is replicated on every rank)
+                parts = [None] * world
+                dist.all_gather_object(parts, outs[k])
+                outs[k] = torch.cat(parts, 0)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, outs)
     lay_reps, shp_reps = [r[1] / a.steps for r in regions], [r[2] / a.steps for r in regions]
-    if fused is not None:
+    if fused is not None and a.full:
         # per-loop figures for the record (outside the timed region): each loop alone on the idle GPU, `reps` times each
         # (the layout loop: 20 untimed steps first, then up to 400 timed ones -- 50 steps right behind a shape loop measured the first
         #  replays of its graph on a GPU still clocked for the matrix work: 0.786 ms where `--workload layout` measures 0.666)
@@ -625,7 +684,7 @@ def main():
             lay_reps.append(e[0].elapsed_time(e[1]) / nl)
             shp_reps.append(e[2].elapsed_time(e[3]) / nn)
         solo = (_stats(lay_reps)['median'] * a.steps, _stats(shp_reps)['median'] * a.steps)
-    if fused_sharded:
+    if fused_sharded and a.full:
         # the layout steps ran inside the sharded main graphs; for the record (outside the timed region): the layout loop alone
         e = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         nn = min(a.steps, 50)
@@ -633,11 +692,11 @@ def main():
         lay_ms = e[0].elapsed_time(e[1]) * a.steps / nn
         lay_reps = [lay_ms / a.steps]
     fused_ms = None
-    if fused is not None:
+    if fused is not None and a.full:
         fused_ms, (lay_ms, shp_ms) = lay_ms, solo
     assert torch.isfinite(st['x']).all(), 'non-finite layout state'
     alt = None
-    if full and sh_world > 1 and not a.check and not a.no_alt_mode:
+    if a.full and full and sh_world > 1 and not a.check and not a.no_alt_mode:
         # The OTHER sharding mode on the same ranks, shape loop only, same K steps inside the same barrier bracket: the line's `value`
         # is the tuned default (or --deterministic); this record puts the other curve next to it, so that one multi-GPU run of the
         # driver shows both (round 6: the canonical arithmetic is that of a 4-object shard, so at N = 8 the two agree).
@@ -682,7 +741,38 @@ def main():
                'kernels_per_step': st['plan'].n_ops, 'launches_per_step': st['plan'].n_launches,
                'weight_bytes_per_step': st['plan'].weight_bytes,
                'hbm_GBps_algorithmic': round(st['plan'].weight_bytes / (lay_ms * 1e-3 / a.steps) / 1e9, 1)}
-        if full:
+        full_metric = ('denoising steps/sec (layout+SDF) for 32-node scene-graph, 64^3 SDF (3x16^3 latent), '
+                       'full step = one DDPM layout step + one DDIM shape step over all objects; `value` = the FUSED step '
+                       '(both loops as one hipGraph per step, the layout step on a parallel branch: what the K timed steps ran); '
+                       '`full_steps_per_s_sum` = SURVEY 8(d)\'s literal 1 / (t_layout_step + t_shape_step), each loop alone')
+        full_dtype = 'f16 MFMA operands / f32 accumulate (shape UNet); f32 (layout, GCN)'
+        full_workload = ('EchoScene full (layout+SDF) %d-node synthetic graph (T=%d), 3x16^3 latent -> '
+                         '64^3 SDF, layout 1000-step DDPM + shape 100-step DDIM schedules; %s'
+                         % (O, T, ('configs[4] shape: %d scenes per GPU x %d GPU(s), partitioned by scene (block-diagonal '
+                                   'batch graph): no per-step collective' % (scenes_local, world)) if weak
+                            else ('1 scene (configs[3] when N > 1: objects sharded over %d GPU(s), echo all-gather of '
+                                  '[O,64] codes every DDIM step over RCCL)' % world)))
+        if full and not a.full:
+            # the plain run: the headline figure of the K timed steps and what identifies the configuration; the per-loop replays,
+            # the roofline, the sub-records and the CPU baseline take runs of their own (--full)
+            out = {
+                'metric': full_metric,
+                'value': round(value, 4), 'unit': 'steps/s', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup,
+                'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True, 'scaling': a.scaling,
+                'vs_baseline': None, 'dtype': full_dtype, 'data': 'synthetic',
+                'config': {'workload': full_workload,
+                           'scenes': scenes, 'hip_graph': use_graph, 'deterministic_shards': a.deterministic if sh_world > 1 else None,
+                           'deterministic': a.deterministic,
+                           'step_graph': os.environ.get('ES_STEP_GRAPH', '0') == '1',
+                           'route_options': route_options_string(),
+                           'loops': 'one hipGraph per full step, layout step as a parallel branch' if fused is not None
+                           else ('layout step as a parallel branch of the sharded main graph' if fused_sharded else 'two HIP streams'),
+                           'layout': {'kernels_per_step': st['plan'].n_ops, 'launches_per_step': st['plan'].n_launches},
+                           'shape': {'kernels_per_step': ss['plan'].n_ops,
+                                     'algorithmic_TFLOP_per_step': round(ss['plan'].flops / 1e12, 3)}},
+                'full': 'per-loop figures, roofline, sub-records and CPU baseline: bench.py --full',
+            }
+        elif full:
             flops = ss['plan'].flops          # this rank's share of the step
             ach_step = flops / (shp_ms * 1e-3 / a.steps) / 1e12
             dom = time_dominant_kernel(ss, dev)
@@ -694,23 +784,15 @@ def main():
                         'measurements, %d repetitions each, and run-to-run variation on one box (see `repetitions`) exceeds the ~1 ms '
                         'the layout branch adds' % (ms_per_step, shp_ms / a.steps, reps))
             out = {
-                'metric': 'denoising steps/sec (layout+SDF) for 32-node scene-graph, 64^3 SDF (3x16^3 latent), '
-                          'full step = one DDPM layout step + one DDIM shape step over all objects; `value` = the FUSED step '
-                          '(both loops as one hipGraph per step, the layout step on a parallel branch: what the K timed steps ran); '
-                          '`full_steps_per_s_sum` = SURVEY 8(d)\'s literal 1 / (t_layout_step + t_shape_step), each loop alone',
+                'metric': full_metric,
                 'value': round(value, 4), 'unit': 'steps/s', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup,
                 'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True, 'scaling': a.scaling,
                 'value_min_max': [rep['value']['min'], rep['value']['max']],
                 'full_steps_per_s_sum': round(1e3 / t_sum, 4),
                 'repetitions': rep, 'note': note,
-                'vs_baseline': None, 'dtype': 'f16 MFMA operands / f32 accumulate (shape UNet); f32 (layout, GCN)',
+                'vs_baseline': None, 'dtype': full_dtype,
                 'data': 'synthetic',
-                'config': {'workload': 'EchoScene full (layout+SDF) %d-node synthetic graph (T=%d), 3x16^3 latent -> '
-                                       '64^3 SDF, layout 1000-step DDPM + shape 100-step DDIM schedules; %s'
-                                       % (O, T, ('configs[4] shape: %d scenes per GPU x %d GPU(s), partitioned by scene (block-diagonal '
-                                                 'batch graph): no per-step collective' % (scenes_local, world)) if weak
-                                          else ('1 scene (configs[3] when N > 1: objects sharded over %d GPU(s), echo all-gather of '
-                                                '[O,64] codes every DDIM step over RCCL)' % world)),
+                'config': {'workload': full_workload,
                            'scenes': scenes, 'hip_graph': use_graph, 'deterministic_shards': a.deterministic if sh_world > 1 else None,
                            'deterministic': a.deterministic,   # ShapeDenoiser(deterministic=...): the canonical arithmetic, bit-exact across world sizes (opt-in since round 6)
                            'step_graph': os.environ.get('ES_STEP_GRAPH', '0') == '1',      # sharded DDIM step captured as ONE graph (opt-in)
@@ -748,7 +830,7 @@ def main():
                 'roofline': {'bound': 'hbm', 'achieved': ach, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                              'frac': round(ach / HBM_PEAK_GBS, 4), 'traffic': pmc_traffic('k_rows_x'), 'traffic_source': pmc_traffic_source(), 'kernel': 'k_rows_x (the rows products of the layout step)'},
             }
-        if world == 1 and not weak and not a.no_sub_records and full:
+        if a.full and world == 1 and not weak and not a.no_sub_records and full:
             out['sub_records'] = sub_records(dev, lay, use_graph, a)
             try:
                 from echoscene_amd import config as escfg
@@ -756,7 +838,7 @@ def main():
                 out['sub_records'].append(fp32_route_record(dev, df, sden, uc, triples_all, escfg.shape_df_conf(224).model.params, use_graph))
             except Exception as exc:                  # (a validation figure must not take the benchmark line down)
                 out['sub_records'].append({'config': 'fp32-operand validation route', 'error': repr(exc)})
-        if world == 1 and not weak and not a.no_cpu_baseline:
+        if a.full and world == 1 and not weak and not a.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(net, obj_embed, triples, O, full, df if full else None, uc if full else None)
         if check is not None:
             out['check'] = check

@@ -562,7 +562,7 @@ def test_bench_two_ranks_on_one_gpu_strong_and_weak():
         env = dict(os.environ, ES_DIST_BACKEND='gloo', MASTER_ADDR='127.0.0.1')
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
                '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
-               '--no-cpu-baseline', '--no-sub-records'] + extra
+               '--full', '--no-cpu-baseline', '--no-sub-records'] + extra
         r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
         lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -598,3 +598,38 @@ def test_bench_two_ranks_on_one_gpu_strong_and_weak():
     assert len(lines) == 1, r.stdout[-1500:]
     d = json.loads(lines[0])
     assert d['n_gpus'] == 2 and (d['check']['latents_crc32'], d['check']['abs_sum']) == crcs[0]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: exactly K timed steps, the headline keys of the line, none of
+    the --full records; --dump-outputs writes the final layout boxes and shape latents as float32 .npy, and two runs with the same
+    arguments write the same arrays (seeded inputs, fixed-order kernels)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK')}
+    dumps = []
+    for run in range(2):
+        out = tmp_path / ('dump%d' % run)
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--nodes', '8',
+               '--dump-outputs', str(out)]
+        r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1, r.stdout[-1500:]
+        d = json.loads(lines[0])
+        for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+            assert k in d, k
+        assert d['steps'] == 3 and d['value'] > 0 and d['unit'] == 'steps/s' and d['higher_is_better'] is True
+        assert abs(d['ms_per_step'] - 1e3 / d['value']) < 1e-2 * d['ms_per_step']
+        for k in ('cpu_baseline', 'sub_records', 'roofline', 'repetitions'):
+            assert k not in d, k
+        arrs = {n: np.load(str(out / (n + '.npy'))) for n in ('layout_boxes', 'shape_latents')}
+        assert arrs['layout_boxes'].dtype == np.float32 and arrs['layout_boxes'].shape[0] == 8
+        assert arrs['shape_latents'].dtype == np.float32 and arrs['shape_latents'].shape == (8, 3, 16, 16, 16)
+        assert all(np.isfinite(v).all() for v in arrs.values())
+        dumps.append(arrs)
+    for n in dumps[0]:
+        assert np.array_equal(dumps[0][n], dumps[1][n]), n

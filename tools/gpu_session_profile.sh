@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/${1:-prof}
 mkdir -p $OUT
-python bench.py --steps 100 --warmup 5 > $OUT/bench_final.json 2> $OUT/bench_final.err
+python bench.py --full --steps 100 --warmup 5 > $OUT/bench_final.json 2> $OUT/bench_final.err
 python bench.py --workload layout --steps 200 --warmup 5 > $OUT/bench_layout.json 2> $OUT/bench_layout.err
 ( cd /tmp && rocprofv3 --kernel-trace --stats -d $OUT/prof_final -o st --output-format csv -- python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 3 --reps 1 --no-cpu-baseline --no-sub-records > $OUT/prof_final.log 2>&1 )
 ( cd /tmp && rocprofv3 --kernel-trace --stats -d $OUT/prof_configs4 -o c4 --output-format csv -- python $GRAFT_REPO_ROOT/bench.py --scaling weak --scenes-per-gpu 8 --steps 4 --warmup 1 --reps 1 --no-cpu-baseline --no-sub-records > $OUT/prof_configs4.log 2>&1 )

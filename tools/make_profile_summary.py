@@ -1,8 +1,8 @@
 #!/usr/bin/env python
-"""Builds profiles/rNN_* from a gpurun_out/ collection:
-   gpurun_out/bench_final.json                     (python bench.py --steps 100 --warmup 5)
-   gpurun_out/prof_final/*/*kernel_stats.csv       (rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline)
-   gpurun_out/pmc_final/<set>/*/*counter_collection.csv   (one rocprofv3 --kernel-trace --pmc <set> pass per counter set)
+"""Builds profiles/rNN_* from a collection directory of GPU-run outputs:
+   <collection>/bench_final.json                   (python bench.py --full --steps 100 --warmup 5)
+   <collection>/prof_final/*/*kernel_stats.csv     (rocprofv3 --kernel-trace --stats --output-format csv -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline)
+   <collection>/pmc_final/<set>/*/*counter_collection.csv (one rocprofv3 --kernel-trace --pmc <set> pass per counter set)
 usage: python tools/make_profile_summary.py r02 [gpurun_out sub-directory]
 Also writes profiles/<tag>_pmc_traffic.json: HBM bytes per launch by kernel family (FETCH_SIZE x 2 -- gfx950 reports half of a
 wide streaming read, MI355X_MICROARCH.md section HBM -- + WRITE_SIZE, both KB in rocprofv3), which bench.py reports as
@@ -31,7 +31,7 @@ for f in glob.glob(os.path.join(go, 'pmc_final', '*', '*', '*counter_collection.
     for r in csv.DictReader(open(f)):
         pmc[short(r['Kernel_Name'])][r['Counter_Name']].append(float(r['Counter_Value']))
 md = ['# Round %s profile summary (MI355X, rocprofv3)\n' % tag[1:],
-      '* `%s_bench_line.json` -- `python bench.py --steps 100 --warmup 5`: **%.2f full steps/s** (one replayed hipGraph per full step, the layout step '
+      '* `%s_bench_line.json` -- `python bench.py --full --steps 100 --warmup 5`: **%.2f full steps/s** (one replayed hipGraph per full step, the layout step '
       'as a parallel branch of the shape step; each loop alone: shape %.2f ms, layout %.3f ms per step), CPU oracle baseline %.5f steps/s on %d host threads; `roofline.achieved` %.1f TFLOP/s for `k_conv_ws` '
       '(avg launch %.1f us, %d launches per step).' % (
           tag, bench['value'], bench['config']['shape']['ms_per_step'], bench['config']['layout']['ms_per_step'],
