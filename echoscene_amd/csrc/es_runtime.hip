@@ -72,6 +72,8 @@ static int dispatch(const es_op& op, hipStream_t s) {
         case ES_OP_STEM: return es_shape_stem(&op.u.stem, s);
         case ES_OP_VQ: return es_vq_lookup(&op.u.vq, s);
         case ES_OP_ROWSEL: return es_row_select(&op.u.rowsel, s);
+        case ES_OP_DDIM_BLEND: return es_ddim_blend(&op.u.blend, s);
+        case ES_OP_CONV_C1: return es_conv_c1_f32(&op.u.conv_c1, s);
         default: es_set_error("plan: unknown op kind %d", op.kind); return 3;
     }
 }
@@ -280,6 +282,12 @@ extern "C" int es_op_pointer_offsets(int kind, size_t* out, int cap) {
             break;
         case ES_OP_VQ: v = {ES_PTR(vq.z), ES_PTR(vq.codebook), ES_PTR(vq.lut), ES_PTR(vq.idx_out), ES_PTR(vq.out_f16)}; break;
         case ES_OP_ROWSEL: v = {ES_PTR(rowsel.table), ES_PTR(rowsel.step), ES_PTR(rowsel.out)}; break;
+        case ES_OP_DDIM_BLEND:
+            v = {ES_PTR(blend.x), ES_PTR(blend.x0), ES_PTR(blend.mask), ES_PTR(blend.noise), ES_PTR(blend.tab), ES_PTR(blend.step)};
+            break;
+        case ES_OP_CONV_C1:
+            v = {ES_PTR(conv_c1.x), ES_PTR(conv_c1.w), ES_PTR(conv_c1.bias), ES_PTR(conv_c1.out_f32), ES_PTR(conv_c1.out_f16)};
+            break;
         case ES_OP_FORK: case ES_OP_JOIN: break;
         default: return -1;
     }

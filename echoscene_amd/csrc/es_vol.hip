@@ -911,8 +911,11 @@ __global__ __launch_bounds__(64 * NW_, 2) void k_conv_lean(const es_conv_args a,
         rB = __builtin_amdgcn_make_buffer_rsrc((void*)(Wg + ((long)by * nks_ph) * (BNP * BK)), (short)0, (int)OOB, 0x00020000);
         const _Float16* Ag = (const _Float16*)(st_phase ? a.a2 : a.a);
         const int Cin = st_phase ? a.Cin2 : a.Cin;
-        const bool down = !st_phase && (a.mode == ES_CONV_DOWN_HW || a.mode == ES_CONV_DOWN_DHW);
-        const bool downd = !st_phase && a.mode == ES_CONV_DOWN_DHW;
+        // DOWN_DHW_P01 (VQ-VAE encoder Downsample: far-face padding only): the tap centre is 2o + 1 instead of 2o; tap_mask27 around
+        // that centre drops exactly the +1 taps of the last output voxel of an axis, and the largest negative tap shift is unchanged
+        const int p01 = (!st_phase && a.mode == ES_CONV_DOWN_DHW_P01) ? 1 : 0;
+        const bool down = !st_phase && (a.mode == ES_CONV_DOWN_HW || a.mode == ES_CONV_DOWN_DHW || p01);
+        const bool downd = !st_phase && (a.mode == ES_CONV_DOWN_DHW || p01);
         const int Dsrc = downd ? 2 * g.D : g.D;
         const int Hi = st_phase ? g.H : g.Hi, Wi = st_phase ? g.W : g.Wi;
         const int ntap = st_phase ? 1 : a.taps;
@@ -928,9 +931,9 @@ __global__ __launch_bounds__(64 * NW_, 2) void k_conv_lean(const es_conv_args a,
         }
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
-            const int ch = down ? 2 * a_h[j] : a_h[j];
-            const int cw = down ? 2 * a_w[j] : a_w[j];
-            const int cd = downd ? 2 * a_d[j] : a_d[j];
+            const int ch = down ? 2 * a_h[j] + p01 : a_h[j];
+            const int cw = down ? 2 * a_w[j] + p01 : a_w[j];
+            const int cd = downd ? 2 * a_d[j] + p01 : a_d[j];
             voff[j] = (unsigned)(((((long)a_o[j] * Dsrc + cd) * Hi + ch) * Wi + cw) * Cin * 2 + a_lc[j] * 16);
             if (UP_) {
                 const int sd = updhw ? a_d[j] >> 1 : a_d[j];
@@ -1240,8 +1243,11 @@ __device__ __forceinline__ void conv_ws_tile(const es_conv_args& a, const ConvGe
             rB = __builtin_amdgcn_make_buffer_rsrc((void*)(Wg + ((long)by * nks_ph) * (BNP * BK)), (short)0, (int)OOB, 0x00020000);
             const _Float16* Ag = (const _Float16*)(st_phase ? a.a2 : a.a);
             const int Cin = st_phase ? a.Cin2 : a.Cin;
-            const bool down = !st_phase && (a.mode == ES_CONV_DOWN_HW || a.mode == ES_CONV_DOWN_DHW);
-            const bool downd = !st_phase && a.mode == ES_CONV_DOWN_DHW;
+            // DOWN_DHW_P01 (VQ-VAE encoder Downsample: far-face padding only): the tap centre is 2o + 1 instead of 2o; tap_mask27 around
+            // that centre drops exactly the +1 taps of the last output voxel of an axis, and the largest negative tap shift is unchanged
+            const int p01 = (!st_phase && a.mode == ES_CONV_DOWN_DHW_P01) ? 1 : 0;
+            const bool down = !st_phase && (a.mode == ES_CONV_DOWN_HW || a.mode == ES_CONV_DOWN_DHW || p01);
+            const bool downd = !st_phase && (a.mode == ES_CONV_DOWN_DHW || p01);
             const int Dsrc = downd ? 2 * g.D : g.D;
             const int Hi = st_phase ? g.H : g.Hi, Wi = st_phase ? g.W : g.Wi;
             const int ntap = st_phase ? 1 : a.taps;
@@ -1257,9 +1263,9 @@ __device__ __forceinline__ void conv_ws_tile(const es_conv_args& a, const ConvGe
             }
 #pragma unroll
             for (int j = 0; j < NA; ++j) {
-                const int ch = down ? 2 * a_h[j] : a_h[j];
-                const int cw = down ? 2 * a_w[j] : a_w[j];
-                const int cd = downd ? 2 * a_d[j] : a_d[j];
+                const int ch = down ? 2 * a_h[j] + p01 : a_h[j];
+                const int cw = down ? 2 * a_w[j] + p01 : a_w[j];
+                const int cd = downd ? 2 * a_d[j] + p01 : a_d[j];
                 voff[j] = (unsigned)(((((long)a_o[j] * Dsrc + cd) * Hi + ch) * Wi + cw) * Cin * 2 + a_lc[j] * 16);
                 if (UP_) {
                     const int sd = updhw ? a_d[j] >> 1 : a_d[j];
@@ -1716,8 +1722,11 @@ __global__ __launch_bounds__(64 * (KS_ * NCH_ + 8), 3) void k_conv_kw(const es_c
             rB = __builtin_amdgcn_make_buffer_rsrc((void*)(Wg + ((long)by * nks_ph) * (BNP * BK)), (short)0, (int)OOB, 0x00020000);
             const _Float16* Ag = (const _Float16*)(st_phase ? a.a2 : a.a);
             const int Cin = st_phase ? a.Cin2 : a.Cin;
-            const bool down = !st_phase && (a.mode == ES_CONV_DOWN_HW || a.mode == ES_CONV_DOWN_DHW);
-            const bool downd = !st_phase && a.mode == ES_CONV_DOWN_DHW;
+            // DOWN_DHW_P01 (VQ-VAE encoder Downsample: far-face padding only): the tap centre is 2o + 1 instead of 2o; tap_mask27 around
+            // that centre drops exactly the +1 taps of the last output voxel of an axis, and the largest negative tap shift is unchanged
+            const int p01 = (!st_phase && a.mode == ES_CONV_DOWN_DHW_P01) ? 1 : 0;
+            const bool down = !st_phase && (a.mode == ES_CONV_DOWN_HW || a.mode == ES_CONV_DOWN_DHW || p01);
+            const bool downd = !st_phase && (a.mode == ES_CONV_DOWN_DHW || p01);
             const int Dsrc = downd ? 2 * g.D : g.D;
             const int Hi = st_phase ? g.H : g.Hi, Wi = st_phase ? g.W : g.Wi;
             const int ntap = st_phase ? 1 : a.taps;
@@ -1733,9 +1742,9 @@ __global__ __launch_bounds__(64 * (KS_ * NCH_ + 8), 3) void k_conv_kw(const es_c
             }
 #pragma unroll
             for (int j = 0; j < JA; ++j) {
-                const int ch = down ? 2 * a_h[j] : a_h[j];
-                const int cw = down ? 2 * a_w[j] : a_w[j];
-                const int cd = downd ? 2 * a_d[j] : a_d[j];
+                const int ch = down ? 2 * a_h[j] + p01 : a_h[j];
+                const int cw = down ? 2 * a_w[j] + p01 : a_w[j];
+                const int cd = downd ? 2 * a_d[j] + p01 : a_d[j];
                 voff[j] = (unsigned)(((((long)a_o[j] * Dsrc + cd) * Hi + ch) * Wi + cw) * Cin * 2 + a_lc[j] * 16);
                 if (UP_) {
                     const int sd = updhw ? a_d[j] >> 1 : a_d[j];
@@ -2901,7 +2910,8 @@ static int conv_dispatch(const es_conv_args* a, es_stream stream, int* emits) {
     g.Hi = a->H; g.Wi = a->W;
     g.Di = a->D;
     if (a->mode == ES_CONV_DOWN_HW) { g.Hi = 2 * a->H; g.Wi = 2 * a->W; }
-    if (a->mode == ES_CONV_DOWN_DHW) { g.Hi = 2 * a->H; g.Wi = 2 * a->W; g.Di = 2 * a->D; }
+    ES_REQUIRE(a->mode >= ES_CONV_SAME && a->mode <= ES_CONV_DOWN_DHW_P01, "es_conv_mfma_f16: unknown mode %d", a->mode);
+    if (a->mode == ES_CONV_DOWN_DHW || a->mode == ES_CONV_DOWN_DHW_P01) { g.Hi = 2 * a->H; g.Wi = 2 * a->W; g.Di = 2 * a->D; }
     if (a->mode == ES_CONV_UP_DHW) g.Di = a->D / 2;
     if (a->mode == ES_CONV_UP_HW || a->mode == ES_CONV_UP_DHW) { g.Hi = a->H / 2; g.Wi = a->W / 2; }
     g.lw = ilog2_exact(a->W); g.lh = ilog2_exact(a->H); g.ld = ilog2_exact(a->D);

@@ -25,6 +25,7 @@ __device__ __forceinline__ long src_row(const es_conv_args& a, const Geom32& g, 
     else if (a.mode == ES_CONV_SAME) { sd = d + kd - 1; sh = h + kh - 1; sw = w + kw - 1; }
     else if (a.mode == ES_CONV_DOWN_HW) { sd = d + kd - 1; sh = 2 * h + kh - 1; sw = 2 * w + kw - 1; }
     else if (a.mode == ES_CONV_DOWN_DHW) { sd = 2 * d + kd - 1; sh = 2 * h + kh - 1; sw = 2 * w + kw - 1; }
+    else if (a.mode == ES_CONV_DOWN_DHW_P01) { sd = 2 * d + kd; sh = 2 * h + kh; sw = 2 * w + kw; }      // far-face padding only
     else {
         // nearest-neighbour up-sampling folded into the gather: the tap addresses the UP-SAMPLED grid (= the output grid)
         const int ud = d + kd - 1, uh = h + kh - 1, uw = w + kw - 1;
@@ -308,7 +309,8 @@ extern "C" int es_conv_f32(const es_conv_args* a, es_stream stream) {
     g.O = a->O; g.D = a->D; g.H = a->H; g.W = a->W;
     g.Di = a->D; g.Hi = a->H; g.Wi = a->W;
     if (a->mode == ES_CONV_DOWN_HW) { g.Hi = 2 * a->H; g.Wi = 2 * a->W; }
-    if (a->mode == ES_CONV_DOWN_DHW) { g.Di = 2 * a->D; g.Hi = 2 * a->H; g.Wi = 2 * a->W; }
+    ES_REQUIRE(a->mode >= ES_CONV_SAME && a->mode <= ES_CONV_DOWN_DHW_P01, "es_conv_f32: unknown mode %d", a->mode);
+    if (a->mode == ES_CONV_DOWN_DHW || a->mode == ES_CONV_DOWN_DHW_P01) { g.Di = 2 * a->D; g.Hi = 2 * a->H; g.Wi = 2 * a->W; }
     if (a->mode == ES_CONV_UP_HW) { g.Hi = a->H / 2; g.Wi = a->W / 2; }
     if (a->mode == ES_CONV_UP_DHW) { g.Di = a->D / 2; g.Hi = a->H / 2; g.Wi = a->W / 2; }
     g.lw = ilog2x(a->W); g.lh = ilog2x(a->H); g.ld = ilog2x(a->D);

@@ -18,11 +18,13 @@ SEG_DIRECT, SEG_GATHER, SEG_CSRMEAN, SEG_CSRSUM, SEG_CSRWAVG = 0, 1, 2, 3, 4
 PRO_NONE, PRO_SILU, PRO_GN, PRO_GN_SILU, PRO_LN, PRO_GEGLU, PRO_LN_ATTN = 0, 1, 2, 3, 4, 5, 6
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_GEGLU, ACT_SIGMOID = 0, 1, 2, 3, 4
 CONV_SAME, CONV_DOWN_HW, CONV_UP_HW, CONV_UP_DHW, CONV_DOWN_DHW = 0, 1, 2, 3, 4
+CONV_DOWN_DHW_P01 = 5                      # the VQ-VAE encoder's Downsample: pad the far face only, stride 2
 EPI_NONE, EPI_GEGLU = 0, 1
 (OP_LINEAR, OP_DDPM, OP_DDIM, OP_COPY, OP_CONV, OP_GN, OP_LN, OP_ATTN, OP_GEGLU, OP_TO_CL, OP_STEM) = range(1, 12)
 OP_VQ = 12
 OP_FORK, OP_JOIN, OP_ROWSEL = 13, 14, 15
 OP_CONV_F32, OP_ATTN_F32 = 16, 17          # fp32-operand validation route (csrc/es_vol32.hip)
+OP_DDIM_BLEND, OP_CONV_C1 = 18, 19         # masked-DDIM blend / the VQ-VAE encoder's one-channel conv_in (csrc/es_keep.hip)
 
 
 class Seg(C.Structure):
@@ -107,10 +109,20 @@ class VQArgs(C.Structure):
                 ('n_embed', C.c_int32), ('Cpad', C.c_int32), ('idx_out', C.c_void_p), ('out_f16', C.c_void_p)]
 
 
+class BlendArgs(C.Structure):
+    _fields_ = [('x', C.c_void_p), ('x0', C.c_void_p), ('mask', C.c_void_p), ('noise', C.c_void_p), ('noise_stride', C.c_int32),
+                ('tab', C.c_void_p), ('step', C.c_void_p), ('O', C.c_int32), ('n', C.c_int32)]
+
+
+class ConvC1Args(C.Structure):
+    _fields_ = [('x', C.c_void_p), ('w', C.c_void_p), ('bias', C.c_void_p), ('out_f32', C.c_void_p), ('out_f16', C.c_void_p),
+                ('O', C.c_int32), ('D', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('N', C.c_int32)]
+
+
 class _OpU(C.Union):
     _fields_ = [('linear', LinearArgs), ('update', UpdateArgs), ('copy', CopyArgs), ('conv', ConvArgs),
                 ('gn', GNArgs), ('ln', LNArgs), ('attn', AttnArgs), ('geglu', GegluArgs), ('tocl', ToClArgs),
-                ('stem', StemArgs), ('vq', VQArgs), ('rowsel', RowSelArgs)]
+                ('stem', StemArgs), ('vq', VQArgs), ('rowsel', RowSelArgs), ('blend', BlendArgs), ('conv_c1', ConvC1Args)]
 
 
 class Op(C.Structure):
@@ -148,6 +160,8 @@ EXPORTS = {
     'es_row_select': (C.c_int, [C.POINTER(RowSelArgs), C.c_void_p]),
     'es_ddpm_update': (C.c_int, [C.POINTER(UpdateArgs), C.c_void_p]),
     'es_ddim_update': (C.c_int, [C.POINTER(UpdateArgs), C.c_void_p]),
+    'es_ddim_blend': (C.c_int, [C.POINTER(BlendArgs), C.c_void_p]),
+    'es_conv_c1_f32': (C.c_int, [C.POINTER(ConvC1Args), C.c_void_p]),
     'es_box_postprocess': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
                                      C.c_void_p]),
     'es_box_descale': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),

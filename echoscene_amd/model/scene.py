@@ -135,6 +135,7 @@ class EchoToShape(object):
     def invalidate(self):
         self._den = None
         self._dec = None
+        self._enc = None
 
     def set_input(self, input=None):
         self.rel = input['c_s']
@@ -158,6 +159,28 @@ class EchoToShape(object):
     def _expected_steps(self):
         return len(range(0, self.df_conf.model.params.timesteps,
                          self.df_conf.model.params.timesteps // self.ddim_steps))
+
+    def _encoder(self):
+        if getattr(self, '_enc', None) is None:
+            from ..samplers import VQEncoder
+            self._enc = VQEncoder(self.vqvae, _hip_device(_dev(self.vqvae)))
+        return self._enc
+
+    def keep_inputs(self, keep_nodes, keep_sdfs, n_objects, device):
+        """``keep_nodes`` / ``keep_sdfs`` of the sampling calls -> (x0 [O,C,D,H,W], mask [O], rows, sdf rows [len(rows),1,64,64,64])
+        of the masked DDIM loop: the kept SDFs go through ``VQVAE.encode_no_quant`` (samplers.VQEncoder)."""
+        from ..samplers import keep_selection
+        keep_nodes = [int(t) for t in (keep_nodes.tolist() if torch.is_tensor(keep_nodes) else keep_nodes)]
+        sdfs = torch.as_tensor(keep_sdfs)
+        if sdfs.dim() != 5 or sdfs.shape[0] != len(keep_nodes) or sdfs.shape[1] != 1:
+            raise ValueError('keep_sdfs must be [len(keep_nodes), 1, D, H, W] (one truncated SDF per entry of keep_nodes); got %s '
+                             'for %d nodes' % (tuple(sdfs.shape), len(keep_nodes)))
+        mask, rows, src = keep_selection(keep_nodes, n_objects)
+        x0 = torch.zeros((n_objects,) + tuple(self.z_shape), device=device)
+        sel = sdfs[src].to(device).float().contiguous() if rows else sdfs[:0].to(device).float()
+        if rows:
+            x0[rows] = self._encoder().encode_no_quant(sel, sync=False)
+        return x0, mask.to(device), rows, sel
 
     def _decoder(self):
         if self._dec is None:
@@ -383,11 +406,20 @@ class Sg2ScDiffModel(_SceneModel):
         return self.ShapeDiff.rel2shape({'obj_cat': dec_objs, 'triples': dec_triples, 'c_s': c, 'uc_s': uc},
                                         noise=shape_noise)
 
-    def _layout_and_shapes(self, gen_shape, dec_objs, dec_triples, obj_embed_, latent, layout_noise, shape_noise):
+    def _layout_and_shapes(self, gen_shape, dec_objs, dec_triples, obj_embed_, latent, layout_noise, shape_noise,
+                           keep_nodes=None, keep_sdfs=None, keep_noise=None):
         """The two loops only share the setup (the reference runs them back to back, EchoScene.py:402-419).  Here they are
         ONE replayed hipGraph: each replay is a DDIM shape step with ten ancestral layout steps on a parallel branch
-        (samplers.sample_layout_and_shape), then the VQ-VAE decode."""
+        (samplers.sample_layout_and_shape), then the VQ-VAE decode.
+
+        ``keep_nodes`` / ``keep_sdfs`` (shape-preserving sampling): the listed nodes keep the SDFs the caller hands in -- their encoded
+        latents follow the forward-noised trajectory of the masked DDIM loop (and take part in every step's message passing) while
+        the other nodes are generated; the returned rows ``keep_nodes`` are the caller's SDFs themselves."""
+        if (keep_nodes is None) != (keep_sdfs is None):
+            raise ValueError('keep_nodes and keep_sdfs go together')
         if not gen_shape:
+            if keep_nodes is not None:
+                raise ValueError('keep_nodes / keep_sdfs keep SHAPES: they need gen_shape=True')
             return None, self._layout(dec_triples, obj_embed_, latent, layout_noise)
         from ..samplers import sample_layout_and_shape
         uc = self._rel_s(obj_embed_)
@@ -401,25 +433,44 @@ class Sg2ScDiffModel(_SceneModel):
         if shape_noise is None:       # the reference seeds this draw from the wall clock (echo2shape.py:502)
             g = torch.Generator(device=sden.device).manual_seed(int(time.time()))
             shape_noise = torch.randn((1,) + tuple(S.z_shape), device=sden.device, generator=g)
+        kw, rows, kept = {}, [], None
+        if keep_nodes is not None:
+            x0, mask, rows, kept = S.keep_inputs(keep_nodes, keep_sdfs, uc.shape[0], sden.device)
+            kw = dict(x0=x0, mask=mask, keep_noise=keep_noise)
         x, z = sample_layout_and_shape(L._denoiser(), sden, obj_embed_, dec_triples, uc, c if need_c else None,
-                                       layout_noise=layout_noise, shape_noise=shape_noise)
+                                       layout_noise=layout_noise, shape_noise=shape_noise, **kw)
         s_, t_ = L.size_dim, L.translation_dim
         boxes = {'sizes': x[:, 0:s_].contiguous(), 'translations': x[:, s_:s_ + t_].contiguous(),
                  'angles': x[:, s_ + t_:L.bbox_dim].contiguous()}
         S.gen_z = z
-        S.gen_df = S._decoder().decode_no_quant(z, sync=True)
+        if rows:
+            # decode only the generated nodes; the kept rows are the caller's SDFs, bit for bit
+            gen = [i for i in range(z.shape[0]) if i not in set(rows)]
+            out = torch.empty((z.shape[0],) + tuple(kept.shape[1:]), device=z.device)
+            if gen:
+                dec = S._decoder().decode_no_quant(z[gen], sync=False)
+                if tuple(dec.shape[1:]) != tuple(kept.shape[1:]):
+                    raise ValueError('keep_sdfs are %s per object, the decoder emits %s' % (tuple(kept.shape[1:]), tuple(dec.shape[1:])))
+                out[gen] = dec
+            out[rows] = kept
+            torch.cuda.synchronize()
+            S.gen_df = out
+        else:
+            S.gen_df = S._decoder().decode_no_quant(z, sync=True)
         return S.gen_df, boxes
 
     @torch.no_grad()
     def sample(self, dec_objs, dec_triplets, dec_text_feat, dec_rel_feat, gen_shape=False, layout_noise=None,
-               shape_noise=None):
-        """EchoScene.py:388-420."""
+               shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None):
+        """EchoScene.py:388-420.  ``keep_nodes`` / ``keep_sdfs`` (keyword-only): see _layout_and_shapes."""
         oe, _, latent_m = self._setup(dec_objs, dec_triplets, dec_text_feat, dec_rel_feat,
                                       dec_objs, dec_triplets, dec_text_feat, dec_rel_feat)
-        sdf, boxes = self._layout_and_shapes(gen_shape, dec_objs, dec_triplets, oe, latent_m, layout_noise, shape_noise)
+        sdf, boxes = self._layout_and_shapes(gen_shape, dec_objs, dec_triplets, oe, latent_m, layout_noise, shape_noise,
+                                             keep_nodes, keep_sdfs, keep_noise)
         return {'shapes': sdf}, boxes
 
-    def _edited(self, enc, dec, touched, added, gen_shape, layout_noise, shape_noise):
+    def _edited(self, enc, dec, touched, added, gen_shape, layout_noise, shape_noise, keep_nodes=None, keep_sdfs=None,
+                keep_noise=None):
         oe, latent, latent_m = self._setup(*enc, *dec, change_rows=touched, added_rows=added)
         if not self.replace_all_latent:
             latent = latent.clone()
@@ -428,7 +479,8 @@ class Sg2ScDiffModel(_SceneModel):
                     latent[t] = latent_m[t]
         else:
             latent = latent_m
-        sdf, boxes = self._layout_and_shapes(gen_shape, dec[0], dec[1], oe, latent, layout_noise, shape_noise)
+        sdf, boxes = self._layout_and_shapes(gen_shape, dec[0], dec[1], oe, latent, layout_noise, shape_noise,
+                                             keep_nodes, keep_sdfs, keep_noise)
         keep = torch.ones(len(boxes['translations']), 1, device=oe.device)
         for t in touched:
             if 0 <= int(t) < keep.shape[0]:
@@ -438,16 +490,16 @@ class Sg2ScDiffModel(_SceneModel):
     @torch.no_grad()
     def sample_with_changes(self, enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triplets,
                             dec_text_feat, dec_rel_feat, manipulated_nodes, gen_shape=False, layout_noise=None,
-                            shape_noise=None):
-        """EchoScene.py:422-472."""
+                            shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None):
+        """EchoScene.py:422-472.  ``keep_nodes`` / ``keep_sdfs`` (keyword-only): see _layout_and_shapes."""
         return self._edited((enc_objs, enc_triples, enc_text_feat, enc_rel_feat),
                             (dec_objs, dec_triplets, dec_text_feat, dec_rel_feat),
-                            list(manipulated_nodes), [], gen_shape, layout_noise, shape_noise)
+                            list(manipulated_nodes), [], gen_shape, layout_noise, shape_noise, keep_nodes, keep_sdfs, keep_noise)
 
     @torch.no_grad()
     def sample_with_additions(self, enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triplets,
                               dec_text_feat, dec_rel_feat, missing_nodes, gen_shape=False, layout_noise=None,
-                              shape_noise=None):
+                              shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None):
         """EchoScene.py:474-532: zero rows inserted at ``missing_nodes[i] + i``; note the reference draws the
         change noise for rows listed in ``missing_nodes`` (:489-494) but splices / masks ``nodes_added``."""
         added = [m + i for i, m in enumerate(missing_nodes)]
@@ -460,7 +512,8 @@ class Sg2ScDiffModel(_SceneModel):
                 latent[t] = latent_m[t]
         else:
             latent = latent_m
-        sdf, boxes = self._layout_and_shapes(gen_shape, dec_objs, dec_triplets, oe, latent, layout_noise, shape_noise)
+        sdf, boxes = self._layout_and_shapes(gen_shape, dec_objs, dec_triplets, oe, latent, layout_noise, shape_noise,
+                                             keep_nodes, keep_sdfs, keep_noise)
         keep = torch.ones(len(boxes['translations']), 1, device=oe.device)
         for t in added:
             keep[t] = 0
@@ -597,8 +650,16 @@ class SGDiff(nn.Module):
         self.diff.invalidate()
         return r
 
+    def _no_keep_without_shapes(self, kw):
+        if self.type_ == 'echolayout' and any(kw.get(k) is not None for k in ('keep_nodes', 'keep_sdfs', 'keep_noise')):
+            raise ValueError("keep_nodes / keep_sdfs keep SHAPES; an 'echolayout' model has no shape branch")
+
     def sample_box_and_shape(self, dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat, gen_shape=False,
                              **noise):
+        """``keep_nodes`` (indices into the decoder-side node list) + ``keep_sdfs`` f32 [K,1,64,64,64] (keyword-only, with
+        gen_shape=True): those nodes keep the given truncated SDFs -- rows ``keep_nodes`` of the returned ``shapes`` are the caller's
+        tensors bit for bit -- and the other nodes are generated in their context (masked DDIM).  Also on the two editing calls."""
+        self._no_keep_without_shapes(noise)
         if self.type_ == 'echolayout':
             return self.diff.sampleBoxes(dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat,
                                          layout_noise=noise.get('layout_noise'))
@@ -609,6 +670,7 @@ class SGDiff(nn.Module):
     def sample_boxes_and_shape_with_changes(self, enc_objs, enc_triples, encoded_enc_text_feat, encoded_enc_rel_feat,
                                             dec_objs, dec_triples, encoded_dec_text_feat, encoded_dec_rel_feat,
                                             manipulated_nodes, gen_shape=False, **noise):
+        self._no_keep_without_shapes(noise)
         if self.type_ == 'echolayout':
             return self.diff.sampleBoxes_with_changes(enc_objs, enc_triples, encoded_enc_text_feat, encoded_enc_rel_feat,
                                                       dec_objs, dec_triples, encoded_dec_text_feat, encoded_dec_rel_feat,
@@ -621,6 +683,7 @@ class SGDiff(nn.Module):
     def sample_boxes_and_shape_with_additions(self, enc_objs, enc_triples, encoded_enc_text_feat, encoded_enc_rel_feat,
                                               dec_objs, dec_triples, encoded_dec_text_feat, encoded_dec_rel_feat,
                                               missing_nodes, gen_shape=False, **noise):
+        self._no_keep_without_shapes(noise)
         if self.type_ == 'echolayout':
             keep, layout_dict = self.diff.sampleBoxes_with_additions(
                 enc_objs, enc_triples, encoded_enc_text_feat, encoded_enc_rel_feat, dec_objs, dec_triples,

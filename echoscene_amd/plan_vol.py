@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import hip
-from .hip import ConvArgs, GNArgs, LNArgs, AttnArgs, GegluArgs, ToClArgs, StemArgs, Op
+from .hip import ConvArgs, GNArgs, LNArgs, AttnArgs, GegluArgs, ToClArgs, StemArgs, BlendArgs, ConvC1Args, Op
 from .plan import (Builder, PackedLinear, GCNWeights, View, seg, emit_gcn, own, mm64)
 
 
@@ -484,6 +484,29 @@ class VolBuilderMixin:
         a.out_is_f32 = 1 if out.dtype == torch.float32 else 0
         return self._push(hip.OP_TO_CL, 'tocl', a)
 
+    def conv_c1(self, x, w, bias, O, dims, out_f32):
+        """Conv3d(1, N, 3, padding 1) of the fp32 volume x [O, D, H, W] -> channels-last fp32 [O*D*H*W, N] (es_conv_c1_f32: the VQ-VAE
+        encoder's conv_in); w f32 [N, 27]"""
+        a = ConvC1Args()
+        a.x, a.w, a.bias = x.data_ptr(), w.data_ptr(), (bias.data_ptr() if bias is not None else None)
+        a.out_f32, a.out_f16 = out_f32.data_ptr(), None
+        a.O, (a.D, a.H, a.W), a.N = O, dims, w.shape[0]
+        self.keep += [w, bias]
+        self.weight_bytes += w.numel() * 4
+        self.flops += 2 * O * dims[0] * dims[1] * dims[2] * 27 * w.shape[0]
+        return self._push(hip.OP_CONV_C1, 'conv_c1', a)
+
+    def blend(self, x, x0, mask, noise, tab, step):
+        """masked-DDIM blend (es_ddim_blend) of the latents x [O, ...] with the forward-noised x0 of the objects whose mask is 1;
+        noise [S, O * n], tab [S, 2] (ShapeSchedule.keep_tab)"""
+        a = BlendArgs()
+        a.x, a.x0, a.mask, a.noise = x.data_ptr(), x0.data_ptr(), mask.data_ptr(), noise.data_ptr()
+        a.O, a.n = x.shape[0], x[0].numel()
+        a.noise_stride = noise.shape[1]
+        a.tab, a.step = tab.data_ptr(), step.data_ptr()
+        self.keep += [x0, mask, noise, tab]
+        return self._push(hip.OP_DDIM_BLEND, 'blend', a)
+
     def stem(self, x, w, scratch, out, O, cin=3, ostride=0):
         a = StemArgs()
         a.x = x.data_ptr()
@@ -777,7 +800,7 @@ def emit_unet3d_step(b, w, g, x, uc_dev, temb, step, eps_out, dims=(16, 16, 16),
     return objbuf
 
 
-for _n in ('_push', 'conv', '_conv32', 'split3', 'conv_gn_intermediate', '_rowgroup_producer', '_rowgroup_stats', 'groupnorm', 'layernorm', 'attention', 'geglu', 'to_cl', 'stem'):
+for _n in ('_push', 'conv', '_conv32', 'split3', 'conv_gn_intermediate', '_rowgroup_producer', '_rowgroup_stats', 'groupnorm', 'layernorm', 'attention', 'geglu', 'to_cl', 'stem', 'conv_c1', 'blend'):
     setattr(Builder, _n, getattr(VolBuilderMixin, _n))
 
 
@@ -788,6 +811,30 @@ for _n in ('_push', 'conv', '_conv32', 'split3', 'conv_gn_intermediate', '_rowgr
 # ------------------------------------------------------------------------------------------------
 def _vq_groups(C):
     return C // 4 if C <= 32 else (32 if C % 32 == 0 else 30)          # Normalize(), vqvae_modules.py:13-21
+
+
+def _vq_res_weights(d, p, device):
+    """ResnetBlock p of a VQ-VAE half (vqvae_modules.py:67-126; d: that half's state dict without its prefix)"""
+    r = dict(gn1=(own(d[p + '.norm1.weight'], device), own(d[p + '.norm1.bias'], device)),
+             conv1=PackedConv(d[p + '.conv1.weight'], d[p + '.conv1.bias'], device),
+             gn2=(own(d[p + '.norm2.weight'], device), own(d[p + '.norm2.bias'], device)),
+             conv2=PackedConv(d[p + '.conv2.weight'], d[p + '.conv2.bias'], device))
+    r['cin'], r['cout'] = d[p + '.conv1.weight'].shape[1], d[p + '.conv1.weight'].shape[0]
+    if (p + '.nin_shortcut.weight') in d:
+        r['skip'] = PackedConv(d[p + '.nin_shortcut.weight'].flatten(1), None, device)
+        r['bias2'] = (d[p + '.conv2.bias'].float() + d[p + '.nin_shortcut.bias'].float()).contiguous().to(device)
+    return r
+
+
+def _vq_attn_weights(d, p, device):
+    """AttnBlock p (vqvae_modules.py:128-176): q | k | v as one product"""
+    Cc = d[p + '.q.weight'].shape[0]
+    return dict(
+        C=Cc, gn=(own(d[p + '.norm.weight'], device), own(d[p + '.norm.bias'], device)),
+        qkv=PackedConv(torch.cat([d[p + '.q.weight'].flatten(1), d[p + '.k.weight'].flatten(1),
+                                  d[p + '.v.weight'].flatten(1)], 0),
+                       torch.cat([d[p + '.q.bias'], d[p + '.k.bias'], d[p + '.v.bias']], 0), device),
+        proj=PackedConv(d[p + '.proj_out.weight'].flatten(1), d[p + '.proj_out.bias'], device))
 
 
 class VQWeights:
@@ -803,27 +850,9 @@ class VQWeights:
             raise NotImplementedError('embed_dim != 3')
         d = {k[len('decoder.'):]: v for k, v in sd.items() if k.startswith('decoder.')}
         self.conv_in = PackedConv(d['conv_in.weight'], d['conv_in.bias'], device)
-
-        def res(p):
-            r = dict(gn1=(own(d[p + '.norm1.weight'], device), own(d[p + '.norm1.bias'], device)),
-                     conv1=PackedConv(d[p + '.conv1.weight'], d[p + '.conv1.bias'], device),
-                     gn2=(own(d[p + '.norm2.weight'], device), own(d[p + '.norm2.bias'], device)),
-                     conv2=PackedConv(d[p + '.conv2.weight'], d[p + '.conv2.bias'], device))
-            r['cin'], r['cout'] = d[p + '.conv1.weight'].shape[1], d[p + '.conv1.weight'].shape[0]
-            if (p + '.nin_shortcut.weight') in d:
-                r['skip'] = PackedConv(d[p + '.nin_shortcut.weight'].flatten(1), None, device)
-                r['bias2'] = (d[p + '.conv2.bias'].float() + d[p + '.nin_shortcut.bias'].float()).contiguous().to(device)
-            return r
-
+        res = lambda p: _vq_res_weights(d, p, device)
         self.mid1, self.mid2 = res('mid.block_1'), res('mid.block_2')
-        p = 'mid.attn_1'
-        Cc = d[p + '.q.weight'].shape[0]
-        self.attn = dict(
-            C=Cc, gn=(own(d[p + '.norm.weight'], device), own(d[p + '.norm.bias'], device)),
-            qkv=PackedConv(torch.cat([d[p + '.q.weight'].flatten(1), d[p + '.k.weight'].flatten(1),
-                                      d[p + '.v.weight'].flatten(1)], 0),
-                           torch.cat([d[p + '.q.bias'], d[p + '.k.bias'], d[p + '.v.bias']], 0), device),
-            proj=PackedConv(d[p + '.proj_out.weight'].flatten(1), d[p + '.proj_out.bias'], device))
+        self.attn = _vq_attn_weights(d, 'mid.attn_1', device)
         n_lvl = 1 + max(int(k.split('.')[1]) for k in d if k.startswith('up.'))
         self.levels = []
         for lvl in reversed(range(n_lvl)):
@@ -837,6 +866,53 @@ class VQWeights:
             self.levels.append((blocks, up))
         self.out_gn = (own(d['norm_out.weight'], device), own(d['norm_out.bias'], device))
         self.conv_out = PackedConv(d['conv_out.weight'], d['conv_out.bias'], device)
+
+
+def _vq_gn(b, st, Oc, x, Cc, ga, be, act, y, raw=None):
+    """Normalize() (+ swish: act 1, GELU: act 2) of the VQ-VAE at the current resolution st['dims'] (vqvae_modules.py:13-21, eps 1e-6)"""
+    dm = st['dims']
+    b.groupnorm(x, Cc, None, 0, Oc, dm[0] * dm[1] * dm[2], ga, be, 1e-6, act, y, raw, groups=_vq_groups(Cc))
+
+
+def _vq_res(b, st, Oc, r):
+    """ResnetBlock (vqvae_modules.py:67-126: swish after both norms, no time embedding, 1x1 nin_shortcut when the channel count
+    changes) on the current activation st['h']"""
+    f16 = torch.float16
+    sbuf = lambda *sh, **kw: b.buf(*sh, scratch=True, **kw)
+    dm = st['dims']
+    M = Oc * dm[0] * dm[1] * dm[2]
+    x, cin, cout = st['h'], r['cin'], r['cout']
+    y1 = sbuf(M, cin, dtype=f16)
+    raw = sbuf(M, cin, dtype=f16) if 'skip' in r else None
+    _vq_gn(b, st, Oc, x, cin, r['gn1'][0], r['gn1'][1], 1, y1, raw)
+    h1 = b.conv_gn_intermediate(y1, r['conv1'], Oc, dm)
+    y2 = sbuf(M, cout, dtype=f16)
+    _vq_gn(b, st, Oc, h1, cout, r['gn2'][0], r['gn2'][1], 1, y2)
+    o = sbuf(M, cout)
+    if 'skip' in r:
+        st['last'] = b.conv(y2, r['conv2'], Oc, dm, bias=r['bias2'], skip=(raw, r['skip']), out_f32=o)
+    else:
+        st['last'] = b.conv(y2, r['conv2'], Oc, dm, res=x, out_f32=o)
+    st.update(h=o, C=cout, h16=None)
+
+
+def _vq_attn(b, st, Oc, at_w):
+    """AttnBlock (vqvae_modules.py:128-176): a single head of C channels over all voxels of the object"""
+    f16 = torch.float16
+    sbuf = lambda *sh, **kw: b.buf(*sh, scratch=True, **kw)
+    dm, Cc = st['dims'], at_w['C']
+    V = dm[0] * dm[1] * dm[2]
+    M = Oc * V
+    x = st['h']
+    yn = sbuf(M, Cc, dtype=f16)
+    _vq_gn(b, st, Oc, x, Cc, at_w['gn'][0], at_w['gn'][1], 0, yn)
+    qkv = sbuf(M, 3 * Cc, dtype=f16)
+    b.conv(yn, at_w['qkv'], Oc, dm, out_f16=qkv)
+    at = sbuf(M, Cc, dtype=f16)
+    b.attention(qkv, Oc, V, 1, Cc, at)
+    o = sbuf(M, Cc)
+    st['last'] = b.conv(at, at_w['proj'], Oc, dm, res=x, out_f32=o)
+    st.update(h=o, h16=None)
 
 
 def emit_vq_decode(b, w, z, sdf_out, Oc, zdims=(16, 16, 16)):
@@ -859,38 +935,10 @@ def emit_vq_decode(b, w, z, sdf_out, Oc, zdims=(16, 16, 16)):
     st['last'] = b.conv(zq, w.conv_in, Oc, zdims, out_f32=o)
     st.update(h=o, C=w.conv_in.N)
 
-    def gn(x, Cc, ga, be, act, y, raw=None):
-        b.groupnorm(x, Cc, None, 0, Oc, V_(st['dims']), ga, be, 1e-6, act, y, raw, groups=_vq_groups(Cc))
-
-    def res(r):
-        dm, M = st['dims'], Oc * V_(st['dims'])
-        x, cin, cout = st['h'], r['cin'], r['cout']
-        y1 = sbuf(M, cin, dtype=f16)
-        raw = sbuf(M, cin, dtype=f16) if 'skip' in r else None
-        gn(x, cin, r['gn1'][0], r['gn1'][1], 1, y1, raw)
-        h1 = b.conv_gn_intermediate(y1, r['conv1'], Oc, dm)
-        y2 = sbuf(M, cout, dtype=f16)
-        gn(h1, cout, r['gn2'][0], r['gn2'][1], 1, y2)
-        o = sbuf(M, cout)
-        if 'skip' in r:
-            st['last'] = b.conv(y2, r['conv2'], Oc, dm, bias=r['bias2'], skip=(raw, r['skip']), out_f32=o)
-        else:
-            st['last'] = b.conv(y2, r['conv2'], Oc, dm, res=x, out_f32=o)
-        st.update(h=o, C=cout, h16=None)
-
+    gn = lambda *a, **kw: _vq_gn(b, st, Oc, *a, **kw)
+    res = lambda r: _vq_res(b, st, Oc, r)
     res(w.mid1)
-    # AttnBlock: single head of C channels over all voxels
-    dm, M, Cc = st['dims'], Oc * V_(st['dims']), w.attn['C']
-    x = st['h']
-    yn = sbuf(M, Cc, dtype=f16)
-    gn(x, Cc, w.attn['gn'][0], w.attn['gn'][1], 0, yn)
-    qkv = sbuf(M, 3 * Cc, dtype=f16)
-    b.conv(yn, w.attn['qkv'], Oc, dm, out_f16=qkv)
-    at = sbuf(M, Cc, dtype=f16)
-    b.attention(qkv, Oc, V_(dm), 1, Cc, at)
-    o = sbuf(M, Cc)
-    st['last'] = b.conv(at, w.attn['proj'], Oc, dm, res=x, out_f32=o)
-    st.update(h=o, h16=None)
+    _vq_attn(b, st, Oc, w.attn)
     res(w.mid2)
     for blocks, up in w.levels:
         for r in blocks:
@@ -907,4 +955,87 @@ def emit_vq_decode(b, w, z, sdf_out, Oc, zdims=(16, 16, 16)):
     yo = sbuf(Oc * V_(dm), st['C'], dtype=f16)
     gn(st['h'], st['C'], w.out_gn[0], w.out_gn[1], 2, yo)        # norm_out -> GELU
     b.conv(yo, w.conv_out, Oc, dm, out_f32=sdf_out, ncdhw=True)
+    return dm
+
+
+# ------------------------------------------------------------------------------------------------
+# VQ-VAE encoder: VQVAE.encode_no_quant (vqvae_networks/network.py:84-88) = Encoder3D.forward (vqvae_modules.py:258-289) ->
+# quant_conv.  The way from an SDF a user HAS to the latent space the shape denoiser works in (shape-preserving sampling).
+# ------------------------------------------------------------------------------------------------
+def fold_quant_conv(sd):
+    """quant_conv (1x1x1, z_channels -> embed_dim) folded into the encoder's conv_out in fp64, the way ``VQWeights.lut`` folds
+    post_quant_conv: quant_conv(conv_out(h)) = (Wq Wo) * h + (Wq bo + bq).  Returns (W [embed_dim, C, 3, 3, 3], b [embed_dim]), fp64."""
+    Wo, bo = sd['encoder.conv_out.weight'], sd['encoder.conv_out.bias']
+    Wq, bq = sd['quant_conv.weight'].flatten(1), sd['quant_conv.bias']
+    if Wo.shape[0] != Wq.shape[1]:
+        raise NotImplementedError('double_z encoders (conv_out has %d channels, quant_conv reads %d) are not supported'
+                                  % (Wo.shape[0], Wq.shape[1]))
+    Wf = mm64(Wq, Wo.flatten(1)).reshape((Wq.shape[0],) + tuple(Wo.shape[1:]))
+    bf = mm64(Wq, bo) + bq.detach().double().to(Wf.device)
+    return Wf, bf
+
+
+class VQEncWeights:
+    """The encoder half of the 'vqvae' checkpoint entry (sd: state dict of model.vqvae.VQVAE) + quant_conv, packed for the volume path."""
+
+    def __init__(self, sd, device):
+        d = {k[len('encoder.'):]: v for k, v in sd.items() if k.startswith('encoder.')}
+        if d['conv_in.weight'].shape[1] != 1:
+            raise NotImplementedError('the encoder reads one-channel SDF volumes')
+        self.conv_in_w = own(d['conv_in.weight'].flatten(1), device)               # [ch, 27] fp32: es_conv_c1_f32
+        self.conv_in_b = own(d['conv_in.bias'], device)
+        self.ch = self.conv_in_w.shape[0]
+        n_lvl = 1 + max(int(k.split('.')[1]) for k in d if k.startswith('down.'))
+        self.levels = []
+        for lvl in range(n_lvl):
+            if any(k.startswith('down.%d.attn.' % lvl) for k in d):
+                raise NotImplementedError('attention inside the encoder levels (attn_resolutions) is not supported')
+            blocks, bi = [], 0
+            while f'down.{lvl}.block.{bi}.norm1.weight' in d:
+                blocks.append(_vq_res_weights(d, f'down.{lvl}.block.{bi}', device))
+                bi += 1
+            down = None
+            if f'down.{lvl}.downsample.conv.weight' in d:
+                down = PackedConv(d[f'down.{lvl}.downsample.conv.weight'], d[f'down.{lvl}.downsample.conv.bias'], device)
+            self.levels.append((blocks, down))
+        self.mid1, self.mid2 = _vq_res_weights(d, 'mid.block_1', device), _vq_res_weights(d, 'mid.block_2', device)
+        self.attn = _vq_attn_weights(d, 'mid.attn_1', device)
+        self.out_gn = (own(d['norm_out.weight'], device), own(d['norm_out.bias'], device))
+        Wf, bf = fold_quant_conv(sd)
+        self.conv_out = PackedConv(Wf.float(), bf.float(), device)
+        self.embed_dim = Wf.shape[0]
+        self.n_down = len([1 for _, dn in self.levels if dn is not None])
+
+
+def emit_vq_encode(b, w, sdf, z_out, Oc, dims=(64, 64, 64)):
+    """sdf f32 [Oc,1,64,64,64] -> z_out f32 [Oc,3,16,16,16] (one chunk of objects).  ``b.tags`` names the activation after conv_in
+    and after every Downsample (parity debugging)."""
+    f16 = torch.float16
+    sbuf = lambda *sh, **kw: b.buf(*sh, scratch=True, **kw)    # activations: not stored in model files
+    st = dict(h=None, C=0, dims=tuple(dims), last=None, h16=None)
+    V_ = lambda dm: dm[0] * dm[1] * dm[2]
+    b.keep.append(w)
+    o = sbuf(Oc * V_(dims), w.ch)
+    b.conv_c1(sdf, w.conv_in_w, w.conv_in_b, Oc, tuple(dims), o)
+    st.update(h=o, C=w.ch)
+    b.tags['conv_in'] = View(o)
+    for lvl, (blocks, down) in enumerate(w.levels):
+        for r in blocks:
+            _vq_res(b, st, Oc, r)
+        if down is not None:
+            dm = st['dims']
+            t = sbuf(Oc * V_(dm), st['C'], dtype=f16)           # f16 copy of the current activation (the Downsample reads it un-normalised)
+            b.ops[st['last']].u.conv.out_f16 = t.data_ptr()
+            nd = (dm[0] // 2, dm[1] // 2, dm[2] // 2)
+            o = sbuf(Oc * V_(nd), st['C'])
+            st['last'] = b.conv(t, down, Oc, nd, mode=hip.CONV_DOWN_DHW_P01, out_f32=o)
+            st.update(h=o, dims=nd, h16=None)
+            b.tags['down.%d' % lvl] = View(o)
+    _vq_res(b, st, Oc, w.mid1)
+    _vq_attn(b, st, Oc, w.attn)
+    _vq_res(b, st, Oc, w.mid2)
+    dm = st['dims']
+    yo = sbuf(Oc * V_(dm), st['C'], dtype=f16)
+    _vq_gn(b, st, Oc, st['h'], st['C'], w.out_gn[0], w.out_gn[1], 2, yo)        # norm_out -> GELU
+    b.conv(yo, w.conv_out, Oc, dm, out_f32=z_out, ncdhw=True)                  # conv_out with quant_conv folded in
     return dm

@@ -7,7 +7,7 @@ import torch
 
 from . import hip
 from .plan import (Builder, GraphIndex, View, GCNWeights, UNet1DWeights, emit_gcn, emit_unet1d_step, time_tables)
-from .plan_vol import UNet3DWeights, emit_unet3d_step, VQWeights, emit_vq_decode
+from .plan_vol import UNet3DWeights, emit_unet3d_step, VQWeights, emit_vq_decode, VQEncWeights, emit_vq_encode
 from .schedules import LayoutSchedule, ShapeSchedule, timestep_embedding_table
 
 
@@ -183,6 +183,7 @@ class ShapeDenoiser:
         self.z_shape = tuple(z_shape)
         self.temb = timestep_embedding_table(self.sched.timesteps, net.model_channels).to(self.device)
         self.coef = self.sched.coef.to(self.device)
+        self.keep_tab = self.sched.keep_tab.to(self.device)      # masked DDIM: q_sample's factors per iteration (es_ddim_blend)
         self.rank, self.world, self.group = rank, world, group
         # deterministic=True ("the 8-GPU result must equal the 1-GPU result bit for bit"): the CANONICAL
         # arithmetic -- every K split and partial-sum tiling is a function of the layer alone: the one a reference shard of
@@ -207,7 +208,10 @@ class ShapeDenoiser:
                 self._fused, self._fused_key = None, None
         self._plans[key] = st
 
-    def _plan_for(self, uc, triples, c=None):
+    def _plan_for(self, uc, triples, c=None, keep=False):
+        """``keep=True``: the plan of the MASKED loop -- one more op, the blend (es_ddim_blend), in front of the step's denoiser ops,
+        and its three inputs: ``x0`` [Ol, C,D,H,W], ``mask`` [Ol], ``knoise`` [S, Ol * latent].  A plan of its own (another cache key):
+        without a mask the plan is, op for op, what it has always been."""
         from .parallel import partition
         uc = uc.reshape(uc.shape[0], -1)
         O = uc.shape[0]
@@ -219,7 +223,7 @@ class ShapeDenoiser:
                                  "no message passing: the cross-attention key [O, 1, context_dim])")
             c = c.reshape(O, -1).to(self.device).float()
         cap = _cap(triples.shape[0])
-        key = (O, cap)
+        key = (O, cap, 'keep') if keep else (O, cap)
         sig = hash(triples.detach().cpu().numpy().tobytes())
         st = self._plans.get(key)
         if st is None:
@@ -242,6 +246,13 @@ class ShapeDenoiser:
             x = b.buf(hi - lo, *self.z_shape)
             eps = b.buf(hi - lo, *self.z_shape)
             step = b.buf(1, dtype=torch.int32, zero=True)
+            kx0 = kmask = knoise = None
+            if keep:
+                # the reference blends before p_sample_ddim (samplers/ddim.py:160-163): the denoiser -- conv-pool stem and shape GCN
+                # included -- reads the kept objects' forward-noised latents, so the generated ones are denoised in their context
+                kx0, kmask = b.buf(hi - lo, *self.z_shape, zero=True), b.buf(hi - lo, zero=True)
+                knoise = b.buf(self.S, x.numel(), zero=True)
+                b.blend(x, kx0, kmask, knoise, self.keep_tab, step)
             ucd = b.dev(uc)
             objbuf = emit_unet3d_step(b, self.w, g, x, ucd, self.temb, step, eps, dims=self.z_shape[1:], lo=lo, hi=hi,
                                       c_dev=c[lo:hi] if need_c else None, tables=self.tables,
@@ -257,7 +268,7 @@ class ShapeDenoiser:
             st = dict(x=x, eps=eps, step=step, snoise=snoise, objbuf=objbuf, ucw=ucd.shape[1], lo=lo, hi=hi, O=O,
                       codes_local=b.codes_local, codes_all=getattr(b, 'codes_all', None), code_cols=b.code_cols,
                       xc=getattr(b, 'xc', None), g=g, pred=getattr(b, 'pred_rows', None), sig=sig,
-                      cdev=getattr(b, 'cdev', None))
+                      cdev=getattr(b, 'cdev', None), x0=kx0, mask=kmask, knoise=knoise)
 
             def sub(ops):
                 b2 = Builder(self.device)
@@ -310,12 +321,15 @@ class ShapeDenoiser:
     def latents_local(self):
         return self._cur['x']
 
-    def save_model(self, path, uc, triples, c=None):
-        """The DDIM loop of this scene (single GPU) as a model file for hosts without Python (es_model_load + es_shape_sample)."""
+    def save_model(self, path, uc, triples, c=None, keep=False):
+        """The DDIM loop of this scene (single GPU) as a model file for hosts without Python (es_model_load + es_shape_sample).
+        ``keep=True``: the masked loop; the host fills the regions "x0" [O,C,D,H,W], "mask" [O] and "keep_noise" [S, O x latent]."""
         from .plan import save_model
         assert self.world == 1 and not self.force_exchange
-        st = self._plan_for(uc, triples, c)
+        st = self._plan_for(uc, triples, c, keep=keep)
         regions = dict(x=st['x'], step=st['step'], coef=self.coef)
+        if keep:
+            regions.update(x0=st['x0'], mask=st['mask'], keep_noise=st['knoise'])
         if st.get('snoise') is not None:
             # ddim_eta != 0: the per-step draws [S, objects x latent] are an INPUT of the loop -- a named region the host fills before
             # es_shape_sample (es_model_region(m, "step_noise")); the file stores whatever the table holds now
@@ -383,14 +397,59 @@ class ShapeDenoiser:
         st['eps_plan'].sample(st['step'], int(iteration), 1, use_graph=False)
         return st['eps'].clone()
 
-    def sample(self, uc, triples, noise1=None, n_steps=None, use_graph=True, c=None, step_noise=None):
+    def _fill_keep(self, st, x0, mask, keep_noise):
+        """inputs of the masked loop into the plan's buffers (this rank's objects lo:hi of the scene's)"""
+        O, lo, hi = st['O'], st['lo'], st['hi']
+        per = 1
+        for d in self.z_shape:
+            per *= int(d)
+        mask = torch.as_tensor(mask, dtype=torch.float32).reshape(-1)
+        if mask.numel() != O or tuple(x0.shape) != (O,) + tuple(self.z_shape):
+            raise ValueError('masked DDIM: x0 must be [O, C, D, H, W] = %s and mask [O]; got %s and %d entries'
+                             % ((O,) + tuple(self.z_shape), tuple(x0.shape), mask.numel()))
+        if not bool(((mask == 0) | (mask == 1)).all()):
+            raise ValueError('masked DDIM: the mask is per object, 0 (generate) or 1 (keep)')
+        if keep_noise is not None and (keep_noise.shape[0] < self.S or keep_noise[0].numel() != O * per):
+            raise ValueError('masked DDIM: keep_noise must be [S, O, C, D, H, W]')
+        full = None
+        if keep_noise is None and self.world > 1:
+            # the table of the WHOLE scene on every rank (an empty one too), then this rank's objects: as the step_noise branch
+            # does, and for the same reason -- ranks seeded alike draw what the unsharded run draws and stay in step
+            full = torch.randn(self.S, O, per, device=self.device)
+        if st.get('empty'):
+            return
+        st['x0'].copy_(x0.to(self.device).float()[lo:hi])
+        st['mask'].copy_(mask.to(self.device)[lo:hi])
+        if full is not None:
+            st['knoise'].copy_(full[:, lo:hi].reshape(self.S, -1))
+        elif keep_noise is None:
+            st['knoise'].normal_()
+        else:
+            kn = keep_noise.to(self.device).float().reshape(keep_noise.shape[0], O, per)[:self.S, lo:hi]
+            st['knoise'].copy_(kn.reshape(self.S, -1))
+
+    def sample(self, uc, triples, noise1=None, n_steps=None, use_graph=True, c=None, step_noise=None, x0=None, mask=None,
+               keep_noise=None):
         """DDIM loop; ``noise1`` f32[1,C,D,H,W] is shared by all objects as in the reference
         (echo2shape.py:507-510); None draws it on the device (world > 1: pass it, or every rank draws its own).
         ``step_noise`` (ddim_eta != 0 only) f32[S, O, C,D,H,W]: the per-step draws of p_sample_ddim, one per OBJECT (noise_like without
         repeat, ldm_diffusion_util.py:289-292); None draws them on the device.
+
+        Masked DDIM (``DDIMSampler.sample(mask=, x0=)``, samplers/ddim.py:160-163) -- keep given shapes while the others are
+        generated: ``mask`` [O] with 1 = keep, 0 = generate, ``x0`` f32[O,C,D,H,W] the kept objects' latents (rows with mask 0 are not
+        read; ``VQEncoder.encode_no_quant`` of their SDFs) and ``keep_noise`` f32[S,O,C,D,H,W] the draws of q_sample (None: drawn on the
+        device).  Before every step the kept rows are set to ``sqrt_ac[t] * x0 + sqrt(1 - ac)[t] * keep_noise[step]``; they take part
+        in the step's echo message passing like every other node.  The reference accepts any tensor as mask; this one is per object,
+        which is what editing a scene needs.  ``mask=None``: the loop and its plan are what they are without this feature.
         Returns the latents of ALL objects [O,C,D,H,W] (all-gathered when sharded)."""
         from .parallel import sharded_ddim_loop
-        st = self._plan_for(uc, triples, c)
+        if (mask is None) != (x0 is None):
+            raise ValueError('masked DDIM needs both x0 and mask')
+        if mask is None and keep_noise is not None:
+            raise ValueError('keep_noise without a mask')
+        st = self._plan_for(uc, triples, c, keep=mask is not None)
+        if mask is not None:
+            self._fill_keep(st, x0, mask, keep_noise)
         n_steps = self.S if n_steps is None else n_steps
         if noise1 is None:
             noise1 = torch.randn((1,) + self.z_shape, device=self.device)
@@ -432,23 +491,44 @@ class ShapeDenoiser:
         return sharded_ddim_loop(self, st['O'], n_steps, self.world, self.group).clone()
 
 
-def sample_layout_and_shape(lay, shp, obj_embed, triples, uc, c=None, layout_noise=None, shape_noise=None, use_graph=True):
+def keep_selection(keep_nodes, n_objects):
+    """``keep_nodes`` (indices into the decoder-side node list) -> (mask f32 [O] with 1 = keep, rows: the kept nodes in ascending
+    order, src: for each of them the row of ``keep_sdfs`` it takes).  Duplicates and out-of-range entries follow the
+    ``manipulated_nodes`` convention (the reference's ``i in list`` tests): a node counts once -- its first entry names its SDF --
+    and an entry outside [0, O) is ignored."""
+    first = {}
+    for k, t in enumerate(keep_nodes):
+        t = int(t)
+        if 0 <= t < n_objects and t not in first:
+            first[t] = k
+    rows = sorted(first)
+    mask = torch.zeros(n_objects, dtype=torch.float32)
+    if rows:
+        mask[rows] = 1.0
+    return mask, rows, [first[t] for t in rows]
+
+
+def sample_layout_and_shape(lay, shp, obj_embed, triples, uc, c=None, layout_noise=None, shape_noise=None, use_graph=True,
+                            x0=None, mask=None, keep_noise=None):
     """Both sampling loops of one scene (EchoScene.py:402-419 runs them back to back) as ONE replayed hipGraph: every replay = one
     DDIM shape step on the main branch and ``T_layout // S_shape`` (= 10) ancestral layout steps on a parallel branch
     (plan.combine_plans), so the latency-bound layout chain -- 131 launches of 32 workgroups per step -- runs inside the gaps
     of the MFMA-bound shape step instead of after it (measured on the bench: 24.3 -> 23.0 ms per full step, i.e. the layout
-    step disappears).  Left-over layout steps (T not a multiple of S) run afterwards.  Returns (boxes x_0 [O, 8], latents z_0)."""
+    step disappears).  Left-over layout steps (T not a multiple of S) run afterwards.  Returns (boxes x_0 [O, 8], latents z_0).
+    ``x0`` / ``mask`` / ``keep_noise``: the masked shape loop (ShapeDenoiser.sample)."""
     from .plan import combine_plans
     if shp.world != 1:
         return lay.sample(obj_embed, triples, noise=layout_noise, use_graph=use_graph), \
-            shp.sample(uc, triples, noise1=shape_noise, c=c, use_graph=use_graph)
+            shp.sample(uc, triples, noise1=shape_noise, c=c, use_graph=use_graph, x0=x0, mask=mask, keep_noise=keep_noise)
     st = lay._plan_for(obj_embed, triples)
     if layout_noise is None:
         st['noise'].normal_()
     else:
         st['noise'][:layout_noise.shape[0]].copy_(layout_noise.to(lay.device))
     st['x'].copy_(st['noise'][0])
-    ss = shp._plan_for(uc, triples, c)
+    ss = shp._plan_for(uc, triples, c, keep=mask is not None)
+    if mask is not None:
+        shp._fill_keep(ss, x0, mask, keep_noise)
     if shape_noise is None:
         shape_noise = torch.randn((1,) + shp.z_shape, device=shp.device)
     ss['x'].copy_(shape_noise.to(shp.device).expand(ss['hi'] - ss['lo'], *shp.z_shape))
@@ -510,6 +590,62 @@ class VQDecoder:
             st['z'].copy_(z[i:i + n])
             st['plan'].run()
             out[i:i + n].copy_(st['sdf'])
+        if sync:
+            torch.cuda.synchronize()
+        return out
+
+
+class VQEncoder:
+    """VQVAE.encode_no_quant on the HIP path (vqvae_networks/network.py:84-88): truncated SDFs [O,1,64,64,64] -> the unquantised latents
+    [O,3,16,16,16] the shape denoiser works on -- ``x0`` of the masked DDIM loop (ShapeDenoiser.sample).  Objects are encoded in chunks
+    (the 64^3 activations are 67 MB per object and fp32 buffer at 64 channels).  The quantised ``encode`` (code indices) is not
+    offered: the loop consumes the unquantised latent, and fp16 operands cannot reproduce an argmin over near-ties."""
+
+    def __init__(self, vqvae, device=None, chunk=8, precision='fp16'):
+        if precision != 'fp16':
+            raise NotImplementedError("VQEncoder: precision %r (only 'fp16': fp16 MFMA operands, fp32 accumulation)" % (precision,))
+        if chunk < 1 or chunk > 8:
+            raise ValueError('VQEncoder: chunk must be 1..8 objects (31-bit byte offsets at 64^3 x 64 channels)')
+        self.device = device or torch.device('cuda')
+        dd = getattr(vqvae, 'ddconfig', None)
+        if dd is not None and dd.get('double_z', False):
+            raise NotImplementedError('VQEncoder: double_z encoders are not supported')
+        self.w = VQEncWeights(state_dict_for(vqvae, self.device), self.device)
+        self.chunk = chunk
+        self._plans = {}
+
+    def _plan(self, Oc, dims):
+        key = (Oc, dims)
+        if key not in self._plans:
+            b = Builder(self.device)
+            sdf = b.buf(Oc, 1, *dims)
+            zd = tuple(d >> self.w.n_down for d in dims)
+            z = b.buf(Oc, self.w.embed_dim, *zd)
+            dm = emit_vq_encode(b, self.w, sdf, z, Oc, dims)
+            assert tuple(dm) == zd, (dm, zd)
+            self._plans = {key: dict(plan=b.finish(), z=z, sdf=sdf)}
+        return self._plans[key]
+
+    def save_model(self, path, n_objects, dims=(64, 64, 64)):
+        """The encoder for ``n_objects`` SDFs as a model file for hosts without Python (es_model_load, regions "sdf" -> "z")."""
+        from .plan import save_model
+        st = self._plan(n_objects, tuple(dims))
+        return save_model(st['plan'], path, dict(sdf=st['sdf'], z=st['z']))
+
+    def encode_no_quant(self, sdf, sync=True):
+        """``sync=False``: everything is only enqueued on the current stream (the caller orders consumers)."""
+        sdf = sdf.to(self.device).float().contiguous()
+        if sdf.dim() != 5 or sdf.shape[1] != 1:
+            raise ValueError('encode_no_quant: sdf must be [O, 1, D, H, W], got %s' % (tuple(sdf.shape),))
+        O = sdf.shape[0]
+        dims = tuple(sdf.shape[2:])
+        out = torch.empty(O, self.w.embed_dim, *[d >> self.w.n_down for d in dims], device=self.device)
+        for i in range(0, O, self.chunk):
+            n = min(self.chunk, O - i)
+            st = self._plan(n, dims)
+            st['sdf'].copy_(sdf[i:i + n])
+            st['plan'].run()
+            out[i:i + n].copy_(st['z'])
         if sync:
             torch.cuda.synchronize()
         return out

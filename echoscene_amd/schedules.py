@@ -124,3 +124,11 @@ class ShapeSchedule:
         self.timesteps = ts[order]
         self.coef = tab[torch.from_numpy(order.copy())].contiguous()        # [S, 4 | 5] by iteration
         self.alphas_cumprod = ac
+        # masked DDIM (keep given shapes, samplers/ddim.py:160-163): q_sample's two factors per iteration, from the MODEL's tables
+        # (register_schedule, echo2shape.py:198-199: sqrt of the float64 cumulative product, then cast to fp32) -- not sqrt() of the
+        # fp32 DDIM alphas above, which may differ in the last bit.  A table of its own: ``coef`` and its stride stay as they are.
+        ac64 = np.cumprod(1.0 - betas, axis=0)
+        self.sqrt_alphas_cumprod = torch.tensor(np.sqrt(ac64), dtype=torch.float32)
+        self.sqrt_one_minus_alphas_cumprod = torch.tensor(np.sqrt(1.0 - ac64), dtype=torch.float32)
+        tsi = torch.from_numpy(self.timesteps.copy())
+        self.keep_tab = torch.stack([self.sqrt_alphas_cumprod[tsi], self.sqrt_one_minus_alphas_cumprod[tsi]], dim=1).contiguous()   # [S, 2] by iteration

@@ -136,3 +136,19 @@ VOCAB = {
     'object_idx_to_name_grained': ['obj%02d' % i for i in range(35)],
     'pred_idx_to_name': ['pred%02d' % i for i in range(16)],
 }
+
+
+def ellipsoid_sdfs(n_objects, seed=0, n=64, trunc=0.2):
+    """Seeded truncated SDFs [n_objects, 1, n, n, n] of axis-aligned ellipsoids on the [-1, 1]^3 grid, clamped to +-trunc as the
+    dataset stores them: centre c ~ U(-0.2, 0.2)^3, radii r ~ U(0.3, 0.7)^3, value (|(p - c) / r| - 1) * min(r).  Inputs of the
+    VQ-VAE encoder tests and goldens -- the formula's parameters are all that has to be stored."""
+    rs = np.random.RandomState(seed)
+    ax = np.linspace(-1.0, 1.0, n)
+    out = np.empty((n_objects, 1, n, n, n), np.float32)
+    for o in range(n_objects):
+        c = rs.uniform(-0.2, 0.2, 3)
+        r = rs.uniform(0.3, 0.7, 3)
+        q = [((ax - c[k]) / r[k]) ** 2 for k in range(3)]
+        d = np.sqrt(q[0][:, None, None] + q[1][None, :, None] + q[2][None, None, :])
+        out[o, 0] = np.clip((d - 1.0) * r.min(), -trunc, trunc).astype(np.float32)
+    return torch.from_numpy(out)

@@ -215,13 +215,30 @@ int es_box_postprocess(float* boxes, int ld, const float* sincos, float* angle_o
  * ncol = 7 -> also column 6, a normalised angle, back to [stats[12], stats[13]] (angle=True, :553-555).  In place. */
 int es_box_descale(float* boxes, int ld, int ncol, const float* stats, int O, es_stream stream);
 int es_ddim_update(const es_update_args* args, es_stream stream);
+/* Masked DDIM (samplers/ddim.py:160-163): before a step's denoiser runs, the latents of the KEPT objects are replaced by the forward-
+ * noised latents of their own shapes, q_sample (echo2shape.py:254-258):
+ *     x[o, :] = mask[o] != 0 ? tab[2*step] * x0[o, :] + tab[2*step + 1] * noise[step][o, :] : x[o, :]
+ * tab = {sqrt_alphas_cumprod[t], sqrt_one_minus_alphas_cumprod[t]} of the step's DDIM timestep t (the MODEL's tables, fp64 -> fp32).
+ * The mask is per object; rows with mask == 0 are neither read nor written.  `step` is read, never advanced.  No fp contraction. */
+typedef struct es_blend_args {
+    float* x;               /* [O, n] latents, kept rows overwritten                            */
+    const float* x0;        /* [O, n] encoded shapes (rows with mask == 0 are not read)         */
+    const float* mask;      /* [O] 0 or 1                                                       */
+    const float* noise;     /* [n_steps][noise_stride]: noise + (*step) * noise_stride + o * n + i */
+    int32_t noise_stride;   /* floats between the steps' draws (>= O * n)                       */
+    const float* tab;       /* [n_steps][2]                                                     */
+    const int32_t* step;
+    int32_t O, n;           /* objects, floats per object (n % 4 == 0)                          */
+} es_blend_args;
+int es_ddim_blend(const es_blend_args* args, es_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * "volume" path -- the 3-D latent-SDF UNet (openai_model_3d.py:816-863).  Activations are
  * channels-last [O, D, H, W, C]; the residual stream is fp32, every contraction reads fp16
  * operands and accumulates in fp32 on MFMA (v_mfma_f32_16x16x32_f16).
  * ---------------------------------------------------------------------------------------- */
-enum { ES_CONV_SAME = 0, ES_CONV_DOWN_HW = 1, ES_CONV_UP_HW = 2, ES_CONV_UP_DHW = 3, ES_CONV_DOWN_DHW = 4 };
+enum { ES_CONV_SAME = 0, ES_CONV_DOWN_HW = 1, ES_CONV_UP_HW = 2, ES_CONV_UP_DHW = 3, ES_CONV_DOWN_DHW = 4,
+       ES_CONV_DOWN_DHW_P01 = 5 };
 
 typedef struct es_conv_args {
     const void* a;            /* f16 [O, D, Hi, Wi, Cin] (channels-last)                         */
@@ -234,7 +251,10 @@ typedef struct es_conv_args {
                                  UP_HW = nearest x2 on H,W folded into addressing (Upsample, :150-153);
                                  UP_DHW = nearest x2 on D,H,W (VQ-VAE Upsample, vqvae_modules.py:24-39; 'concat' UNet,
                                  dims=4, openai_model_3d.py:155-156); DOWN_DHW = stride 2 on D,H,W ('concat' UNet
-                                 Downsample with dims=4, :188)                                              */
+                                 Downsample with dims=4, :188); DOWN_DHW_P01 = the VQ-VAE encoder's Downsample
+                                 (vqvae_modules.py:42-61): F.pad(x, (0,1,0,1,0,1)) then stride 2 without padding -- output
+                                 voxel o reads inputs 2o, 2o+1, 2o+2 on each axis, zero beyond the FAR face only (DOWN_DHW
+                                 pads both faces and reads 2o-1 .. 2o+1)                                    */
     /* optional second contraction accumulated into the same tile: the 1x1 skip_connection of a
        ResBlock whose channel count changes (out = conv2(h) + skip(x), :294-314) */
     const void* a2; const void* w2; int32_t Cin2;
@@ -381,6 +401,19 @@ typedef struct es_vq_args {
 } es_vq_args;
 int es_vq_lookup(const es_vq_args* args, es_stream stream);
 
+/* The VQ-VAE encoder's conv_in (Encoder3D, vqvae_modules.py:205-209): Conv3d(1, N, 3, padding 1) over a one-channel volume, fp32 in,
+ * fp32 FMA (27 taps in (kd, kh, kw) order, then + bias), channels-last fp32 out -- a write-bound kernel: the MFMA kernels would need
+ * the single input channel padded to 32.  D, H % 4 == 0, W % 16 == 0, N = 16, 32, 64 or 128. */
+typedef struct es_conv_c1_args {
+    const float* x;          /* [O, D, H, W] fp32 (NCDHW with C = 1)                             */
+    const float* w;          /* [N][27] fp32 (the PyTorch weight [N,1,3,3,3])                    */
+    const float* bias;       /* [N] or NULL                                                      */
+    float* out_f32;          /* [O*D*H*W, N] channels-last, or NULL                              */
+    void* out_f16;           /* optional f16 copy [O*D*H*W, N], or NULL                          */
+    int32_t O, D, H, W, N;
+} es_conv_c1_args;
+int es_conv_c1_f32(const es_conv_c1_args* args, es_stream stream);
+
 /* NCDHW fp32 latent <-> channels-last helpers, the 3->32->64 conv-pool stem of
  * shape_messsage_passing (openai_model_3d.py:757-764). */
 int es_latent_to_cl_f16(const float* x_ncdhw, int O, int C, int V, int Cpad, void* out_f16, es_stream s);
@@ -406,7 +439,9 @@ enum {
     ES_OP_LINEAR = 1, ES_OP_DDPM = 2, ES_OP_DDIM = 3, ES_OP_COPY = 4, ES_OP_CONV = 5, ES_OP_GN = 6,
     ES_OP_LN = 7, ES_OP_ATTN = 8, ES_OP_GEGLU = 9, ES_OP_TO_CL = 10, ES_OP_STEM = 11, ES_OP_VQ = 12,
     ES_OP_FORK = 13, ES_OP_JOIN = 14, ES_OP_ROWSEL = 15,
-    ES_OP_CONV_F32 = 16, ES_OP_ATTN_F32 = 17      /* the fp32-operand validation route: es_conv_f32 / es_attention_f32 on the same argument structs */
+    ES_OP_CONV_F32 = 16, ES_OP_ATTN_F32 = 17,     /* the fp32-operand validation route: es_conv_f32 / es_attention_f32 on the same argument structs */
+    ES_OP_DDIM_BLEND = 18,                        /* es_ddim_blend (es_blend_args): the masked-DDIM blend in front of a step's denoiser */
+    ES_OP_CONV_C1 = 19                            /* es_conv_c1_f32 (es_conv_c1_args): the VQ-VAE encoder's one-channel conv_in */
 };
 /* Row select: out[r, 0..n) = table[*step, 0..n) for r < rows.  The timestep-dependent but node-independent products of a
  * denoiser (time MLP, all ResBlock emb projections, box/shape time embedding) are tabulated once per schedule
@@ -431,7 +466,7 @@ typedef struct es_op {
     union {
         es_linear_args linear; es_update_args update; es_copy_args copy; es_conv_args conv;
         es_gn_args gn; es_ln_args ln; es_attn_args attn; es_geglu_args geglu; es_tocl_args tocl;
-        es_stem_args stem; es_vq_args vq; es_rowsel_args rowsel;
+        es_stem_args stem; es_vq_args vq; es_rowsel_args rowsel; es_blend_args blend; es_conv_c1_args conv_c1;
     } u;
 } es_op;
 
@@ -497,6 +532,7 @@ int es_sampler_run(es_plan* plan, int32_t* step, int first_step, int n_steps, in
  *   both loops  :  "coef" = the schedule's coefficient table [n_steps][coef_stride]: es_model_run / es_layout_sample / es_shape_sample
  *                  refuse to run past its last row
  *   vq model    :  "z" [O,3,16,16,16] input latents, "sdf" [O,1,64,64,64] output
+ *   vq encoder  :  "sdf" [O,1,64,64,64] input, "z" [O,3,16,16,16] output (VQVAE.encode_no_quant; run with es_model_run(m, 0, 1, s))
  * ---------------------------------------------------------------------------------------- */
 typedef struct es_model es_model;
 typedef struct es_buffer_desc { const void* ptr; size_t bytes; } es_buffer_desc;
