@@ -16,7 +16,8 @@
 #include <string>
 #include <algorithm>
 #include <cstdlib>
-#include <mutex>
+#include <initializer_list>
+#include <utility>
 #include <type_traits>
 
 namespace {
@@ -1438,7 +1439,10 @@ __global__ __launch_bounds__(64 * (NC_ + NP_), 3) void k_conv_ws(const es_conv_a
 // clock = 920 clocks, next to 896 clocks of MFMA issue -- both pipes are co-critical (profiles/r06_notes.md section 4).  Same
 // products in the same order: bit-identical to k_conv_ws.  (Round 2 had tried the shared A tile with shifted LDS reads of a
 // halo'd tile: +6 %; here the shift costs 8 VALU moves per fragment pair and no LDS access.)
-// Ring: 4 B slots (one per K unit) + 2 A slots (one per group) = 96 KB, as k_conv_ws; one barrier per K unit.
+// ONE barrier per (chunk, kd, kh) group, not one per K unit: the producers issue a whole group (its A tile and three B tiles) right
+// after the barrier that publishes the previous one.  Ring: 7 B slots (the tile still being read + one group published + one
+// landing) + 2 A slots (one per group) = 144 KB.  (One barrier per K unit on a 4 + 2 slot ring was the first form: slower,
+// profiles/r06_conv_launch_ab.txt.)
 // ---------------------------------------------------------------------------------------------
 typedef int i4v __attribute__((ext_vector_type(4)));
 template <int DIR>      // -1: lane w takes lane w - 1 (tap kw = -1), +1: lane w takes lane w + 1 (tap kw = +1); zero past the row's ends
@@ -1452,12 +1456,9 @@ __device__ __forceinline__ h8 a3_shift(const h8 v, const bool zero_lane) {
     return __builtin_bit_cast(h8, x);
 }
 
-// GB_: ONE barrier per (chunk, kd, kh) group instead of one per K unit -- the producers issue a whole group (its A tile and three B
-// tiles) right after the barrier that publishes the previous one; 7 B slots (the tile still being read + one group published + one
-// landing) + 2 A slots = 144 KB.
-template <bool STATS_, bool GB_ = false>
+template <bool STATS_>
 __global__ __launch_bounds__(768, 3) void k_conv_ws3(const es_conv_args a, const ConvGeom g) {
-    constexpr int BM_ = 256, NC_ = 8, NP_ = 4, NSB = GB_ ? 7 : 4, NSA = 2, MI = 4;
+    constexpr int BM_ = 256, NC_ = 8, NP_ = 4, NSB = 7, MI = 4;
     constexpr int A_BYTES = BM_ * BK * 2, B_BYTES = BNP * BK * 2, A_RING = NSB * B_BYTES;      // A slots behind the B ring
     constexpr int NA = (BM_ / 16) / NP_, NB = (BNP / 16) / NP_;
     constexpr unsigned OOB = 0x80000000u;
@@ -1523,44 +1524,24 @@ __global__ __launch_bounds__(768, 3) void k_conv_ws3(const es_conv_args a, const
             }
             b_off += (unsigned)B_BYTES;
         };
-        if constexpr (GB_) {
-            int sb = 0;
-            auto issue_group = [&](int gi) __attribute__((always_inline)) {
-                issue_A(gi & 1);
+        int sb = 0;
+        auto issue_group = [&](int gi) __attribute__((always_inline)) {
+            issue_A(gi & 1);
 #pragma unroll
-                for (int t = 0; t < 3; ++t) { issue_B(sb); sb = sb == NSB - 1 ? 0 : sb + 1; }
-            };
-            issue_group(0);
-            for (int gi = 0; gi < ngrp; ++gi) {
-                wait_vmcnt<0>();                     // group gi landed (it is the only one in flight)
-                __builtin_amdgcn_s_barrier();        // group gi visible; every consumer is past the first two units of group gi - 1
-                if (gi + 1 < ngrp) issue_group(gi + 1);
-            }
-            __builtin_amdgcn_s_barrier();            // (the consumers' barrier behind the last group)
-            f4 dummy[MI][7];
-            conv_epilogue<BM_, NC_, false, true, ES_EPI_NONE, false, STATS_>(a, g, dummy, smem, M, m0, n0, wave, lane, S, bz, 0);
-            return;
+            for (int t = 0; t < 3; ++t) { issue_B(sb); sb = sb == NSB - 1 ? 0 : sb + 1; }
+        };
+        issue_group(0);
+        for (int gi = 0; gi < ngrp; ++gi) {
+            wait_vmcnt<0>();                     // group gi landed (it is the only one in flight)
+            __builtin_amdgcn_s_barrier();        // group gi visible; every consumer is past the first two units of group gi - 1
+            if (gi + 1 < ngrp) issue_group(gi + 1);
         }
-        issue_A(0);
-        issue_B(0);
-        if (nloc > 1) issue_B(1);
-        int kw3 = 0, grp = 0;
-        for (int u = 0; u < nloc; ++u) {
-            // loads issued AFTER the ones unit u needs: B(u + 1), and the next group's A tile when u is not a group's first unit
-            const int newer = (u + 1 < nloc ? NB : 0) + ((kw3 != 0 && grp + 1 < ngrp) ? NA : 0);
-            if (newer >= NA + NB) wait_vmcnt<NA + NB>(); else if (newer >= NB) wait_vmcnt<NB>(); else wait_vmcnt<0>();
-            __builtin_amdgcn_s_barrier();            // unit u (and its group's A tile) visible; the slots behind released
-            if (u + 2 < nloc) issue_B((u + 2) % NSB);
-            if (kw3 == 0 && grp + 1 < ngrp) issue_A((grp + 1) % NSA);
-            if (++kw3 == 3) { kw3 = 0; ++grp; }
-        }
-        __builtin_amdgcn_s_barrier();                // (the consumers' barrier behind the last unit: their loop is straight-line)
+        __builtin_amdgcn_s_barrier();            // (the consumers' barrier behind the last group)
         f4 dummy[MI][7];
         conv_epilogue<BM_, NC_, false, true, ES_EPI_NONE, false, STATS_>(a, g, dummy, smem, M, m0, n0, wave, lane, S, bz, 0);
         return;
     }
     // =============================== consumer ===============================
-    static_assert(NA == NB, "the producer's wait ladder assumes equal A and B piece counts per wave");
     const int wm = wave >> 1, wn = wave & 1;
     f4 acc[MI][7];
 #pragma unroll
@@ -1574,7 +1555,7 @@ __global__ __launch_bounds__(768, 3) void k_conv_ws3(const es_conv_args a, const
     // MFMA order: B column outer, A row inner -- one B fragment is live at a time (3 in a prefetch ring) instead of all 7, which pays for
     // the 4 shifted A fragments of the kw = -1 / +1 units inside the 168-register budget (112 accumulators + 16 centre + 16 shifted +
     // 12 B).  The current unit's B slot is therefore read until the END of the unit, past the barrier that publishes the next one:
-    // the B ring has 4 slots (the producers refill slot u % 4 after barrier u + 2, when every consumer has left unit u).
+    // the B ring has 7 slots (a group's three slots are refilled two group barriers later, when every consumer has left the group).
     h8 afc[MI], bq[3];
     __builtin_amdgcn_s_barrier();                                           // unit 0 and group 0 published
     bq[0] = *(const h8*)(smem + fragB);
@@ -1607,7 +1588,7 @@ __global__ __launch_bounds__(768, 3) void k_conv_ws3(const es_conv_args a, const
                 for (int i = 0; i < MI; ++i)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(KW == 1 ? afc[i] : ash[i], bq[(C0 + j) % 3], acc[i][j], 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
-                if (j == 0 && (!GB_ || KW == 2)) __builtin_amdgcn_s_barrier();   // the next unit (after kw = +1: the next group's A tile) published; GB_: the next GROUP
+                if (j == 0 && KW == 2) __builtin_amdgcn_s_barrier();   // the next GROUP (its A tile and three B tiles) published
                 // the fragment of column j + 3 into the buffer column j has just released: two columns of MFMAs (of both SIMD partners) cover
                 // the read (with "column j + 2 into the buffer of column j - 1" the compiler's waitcnt sat one column behind every read)
                 // (the fragment of column j + 2 into the buffer of column j - 1.  Three columns ahead -- into the buffer column j has just
@@ -1909,10 +1890,10 @@ __global__ __launch_bounds__(64 * (KS_ * NCH_ + 8), 3) void k_conv_kw(const es_c
 // epilogue of tile c overlaps the loads of tile c+1 (the epilogue slabs live BEHIND the ring: no workgroup barrier in it).
 // Same tile, LDS image, K order and arithmetic as k_conv_ws (results are bit-identical).
 // ---------------------------------------------------------------------------------------------
-template <int EPI_, int NS_ = 3>
+template <int EPI_>
 __global__ __launch_bounds__(768, 3) void k_linear_ws(const es_conv_args a, const ConvGeom g, int ncb) {
-    // ring depth NS_: 3; 4 (ES_LIN_RING=4, GEGLU variant only: its fp16 epilogue slabs leave the room) measured neutral
-    constexpr int BM_ = 256, NC_ = 8, NP_ = 4, NS = NS_;
+    // ring depth 3 (a fourth slot behind the GEGLU variant's fp16 epilogue slabs measured neutral, profiles/r04_notes.md)
+    constexpr int BM_ = 256, NC_ = 8, NP_ = 4, NS = 3;
     constexpr int WROWS = BM_ / (NC_ / 2), MI = WROWS / 16;
     constexpr int A_BYTES = BM_ * BK * 2, B_BYTES = BNP * BK * 2, STAGE_BYTES = A_BYTES + B_BYTES, RING_BYTES = NS * STAGE_BYTES;
     constexpr int NA = (BM_ / 16) / NP_, NB = (BNP / 16) / NP_, NLOAD = NA + NB;
@@ -2044,7 +2025,10 @@ __global__ __launch_bounds__(768, 3) void k_linear_ws(const es_conv_args a, cons
 #ifdef ES_STAMP
         if (cb < 3) ES_STAMP_AT(1 + 2 * cb);
 #endif
-        conv_epilogue<BM_, NC_, true, true, EPI_, true>(a, g, acc, smem + RING_BYTES, M, m0, (by0 + cb) * BN, wave, lane, 1, 0, 0);
+        // (RING_BYTES through readfirstlane, which folds to the constant once the epilogue is inlined: as a plain constant the LDS base
+        //  is propagated into conv_epilogue BEFORE inlining when this is its only caller, and the GEGLU variant then spills two more
+        //  dwords -- the kernel measured since round 4 escaped that only while a four-slot sibling, since deleted, passed another base)
+        conv_epilogue<BM_, NC_, true, true, EPI_, true>(a, g, acc, smem + __builtin_amdgcn_readfirstlane(RING_BYTES), M, m0, (by0 + cb) * BN, wave, lane, 1, 0, 0);
 #ifdef ES_STAMP
         if (cb < 3) ES_STAMP_AT(2 + 2 * cb);
 #endif
@@ -2799,6 +2783,9 @@ extern "C" int es_pack_conv_rows_f16(const float* h_w, int N, int CinW, int taps
 // ranks -- or a process that saves a model file and one that replays it -- with different environments silently disagreed (ADVICE r4,
 // VERDICT r4 #6).  Now they are process-wide options with constant defaults that ONLY an explicit es_vol_set_option() call changes
 // (tests and A/B tools); es_model_save records them in the file and es_model_load refuses a file written under other values.
+// conv_route() below is the only reader of the conv_* options (gn_rg: es_groupnorm_vol).  Next to them it reads three environment switches -- ES_CONV_A3, ES_CONV_LINWS,
+// ES_CONV_N16 -- that move a launch between kernels with the same K order and the same bits; the A/B switches
+// whose variant lost (ES_CONV_NS, ES_CONV_GB, ES_LIN_RING, ES_LIN_NCB_MAX) went with the kernel variants only they reached.
 #ifndef ES_CONV_A3_DEFAULT
 #define ES_CONV_A3_DEFAULT true
 #endif
@@ -2835,69 +2822,59 @@ extern "C" int es_vol_options(char* out, int cap) {
     return (int)s.size() + 1;
 }
 
-// k_conv_ws launcher for one (tile rows, consumer waves, producer waves, ring depth): the 256-row tile of rounds 1-5 (8 consumers as
-// 4 x 2, 4 producers) and, round 6, the few-objects tiles of 64 / 128 rows (4 consumers as 2 x 2 of BM_/2 x 112, 4 or 8 producers,
-// deeper rings).  The instantiation's dynamic-LDS limit is set once per process.
-template <int BM_, int NC_, int NP_, int NS_>
-static int launch_ws(const es_conv_args* a, const ConvGeom& g, int ncdhw, dim3 grid, hipStream_t st, bool upm, bool geglu, bool stats) {
-    constexpr int LDS = NS_ * (BM_ * BK * 2 + BNP * BK * 2);
-    constexpr bool CAN_STATS = BM_ / (NC_ / 2) == 64;             // row-group sums are per 64-row wave
-    static_assert(LDS <= 160 * 1024, "ring exceeds the CU's LDS");
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [] {
-        auto set = [](const void* f) {
-            const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            if (e != hipSuccess && attr_err == hipSuccess) attr_err = e;
-        };
-        set((const void*)k_conv_ws<BM_, NC_, NP_, false, ES_EPI_NONE, false, NS_>);
-        set((const void*)k_conv_ws<BM_, NC_, NP_, true, ES_EPI_NONE, false, NS_>);
-        set((const void*)k_conv_ws<BM_, NC_, NP_, false, ES_EPI_GEGLU, false, NS_>);
-        if constexpr (CAN_STATS) {
-            set((const void*)k_conv_ws<BM_, NC_, NP_, false, ES_EPI_NONE, true, NS_>);
-            set((const void*)k_conv_ws<BM_, NC_, NP_, true, ES_EPI_NONE, true, NS_>);
-        }
-    });
-    ES_REQUIRE(attr_err == hipSuccess, "es_conv_mfma_f16: hipFuncSetAttribute failed: %s", hipGetErrorString(attr_err));
-    const dim3 blk(64 * (NC_ + NP_));
-    if (geglu) hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, false, ES_EPI_GEGLU, false, NS_>), grid, blk, LDS, st, *a, g, ncdhw);
-    else if (stats) {
-        if constexpr (CAN_STATS) {
-            if (upm) hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, true, ES_EPI_NONE, true, NS_>), grid, blk, LDS, st, *a, g, ncdhw);
-            else hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, false, ES_EPI_NONE, true, NS_>), grid, blk, LDS, st, *a, g, ncdhw);
-        } else ES_REQUIRE(false, "launch_ws: row-group sums need 64-row waves");
+namespace {
+// The dynamic-LDS limits of a launch site's kernels, raised when the site's function-local static of this type is constructed: once
+// per process (per instantiation of a templated site), thread-safe; err is the first failure.  A site that lists several kernels
+// fails as a whole: conv_launch()'s one list means a failure on any of its kernels fails every conv launch of the process.
+struct LdsLimits {
+    hipError_t err = hipSuccess;
+    LdsLimits(std::initializer_list<std::pair<const void*, int>> kernels) {
+        for (const auto& k : kernels)
+            if (const hipError_t e = hipFuncSetAttribute(k.first, hipFuncAttributeMaxDynamicSharedMemorySize, k.second); err == hipSuccess) err = e;
     }
-    else if (upm) hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, true, ES_EPI_NONE, false, NS_>), grid, blk, LDS, st, *a, g, ncdhw);
-    else hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, false, ES_EPI_NONE, false, NS_>), grid, blk, LDS, st, *a, g, ncdhw);
-    return 0;
-}
+};
 
-// k_conv_kw: K split inside the workgroup (KS_ streams x NCH_ column halves of 112)
-template <int KS_, int NCH_>
-static int launch_kw(const es_conv_args* a, const ConvGeom& g, int ncdhw, long M, int ntn, int S, hipStream_t st, bool upm, bool geglu) {
-    constexpr int RING = 3 * KS_ * (64 * BK * 2 + NCH_ * 112 * BK * 2), PART = 4 * 112 * 64 * 4;
-    constexpr int LDS = RING > PART ? RING : PART;
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    std::call_once(once, [] {
-        auto set = [](const void* f) {
-            const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-            if (e != hipSuccess && attr_err == hipSuccess) attr_err = e;
-        };
-        set((const void*)k_conv_kw<KS_, NCH_, false, ES_EPI_NONE>);
-        set((const void*)k_conv_kw<KS_, NCH_, true, ES_EPI_NONE>);
-        set((const void*)k_conv_kw<KS_, NCH_, false, ES_EPI_GEGLU>);
-    });
-    ES_REQUIRE(attr_err == hipSuccess, "es_conv_mfma_f16: hipFuncSetAttribute failed: %s", hipGetErrorString(attr_err));
-    const dim3 grid((unsigned)((M + 63) / 64), (unsigned)(ntn * (2 / NCH_)), (unsigned)S), blk(768);
-    if (geglu) hipLaunchKernelGGL((k_conv_kw<KS_, NCH_, false, ES_EPI_GEGLU>), grid, blk, LDS, st, *a, g, ncdhw);
-    else if (upm) hipLaunchKernelGGL((k_conv_kw<KS_, NCH_, true, ES_EPI_NONE>), grid, blk, LDS, st, *a, g, ncdhw);
-    else hipLaunchKernelGGL((k_conv_kw<KS_, NCH_, false, ES_EPI_NONE>), grid, blk, LDS, st, *a, g, ncdhw);
-    return 0;
-}
+// ---- The route of one es_conv_mfma_f16 launch ------------------------------------------------------------------------------------
+// conv_route() DECIDES (host arithmetic on the arguments, the route options and three environment switches: no HIP call), conv_launch()
+// LAUNCHES what the route names and decides nothing, the planner's queries (es_conv_emits_gn_stats / _gn_part / es_conv_split_of) read
+// a field.  Shard bit-equality, the workspace's slab count and a model file's replay all rest on this rule: keep it in conv_route().
+// The kernel families; k_conv_ws has one value per tile built: rows, consumer waves, producer waves, ring depth
+enum class ConvKernel {
+    none,                      // nothing conv_launch() can launch: a chunked route, or forcing options that name a tile that is not built
+    small_n, small_n_tiled, n16, kw_4_1, kw_2_2, ws_256_8_4_3, ws_64_4_4_3, ws_64_4_4_6, ws_128_4_4_3, ws_128_4_8_3, ws_128_4_8_5, ws3,
+    linear_ws, linear_deep, lean_256, lean_128, lean_64
+};
+enum class ConvReduce { none, plain, gn_part };      // k_conv_splitk_reduce / k_conv_splitk_reduce_gn behind a launch split over workgroups
+struct ConvRoute {
+    ConvGeom g;
+    int ncdhw;
+    long M;                    // rows of this launch
+    long omax;                 // > 0: over the 2 GiB descriptor limit -- launched in chunks of omax objects, each with a route of its own
+    ConvKernel kernel;
+    dim3 grid;
+    size_t lds;                // small_n / small_n_tiled: dynamic LDS bytes (the other kernels' are constants of their launchers)
+    int S;                     // split of K over workgroups (grid.z; 1: none)
+    int ncb;                   // linear_ws: column tiles a workgroup walks
+    bool upm, geglu;
+    char unbuilt[96];          // kernel == none behind forcing options: what conv_launch() reports
+    bool epi_stats;            // the kernel's epilogue can form the row-group sums of gn_stats_out (es_conv_emits_gn_stats)
+    bool stats;                // ... and does in this launch: gn_stats_out is given
+    bool part_ok;              // the reduction can form a GroupNorm's per-tile partial sums (es_conv_emits_gn_part)
+    ConvReduce reduce;
+    int vt;                    // gn_part: voxel tile of the partial sums
+    bool stats_pass;           // k_rowgroup_stats over the finished output forms gn_stats_out
+    int slabs;                 // es_conv_split_of: fp32 slabs [slabs][M][N] written into the workspace (a chunked launch: in units of the
+                               // whole M x N; 0: a direct kernel, no workspace; for linear_deep the automatic split it stands in for)
+};
+}  // namespace
 
-// emits != nullptr: dry run -- report whether this launch would form gn_stats_out in its epilogue, launch nothing
-static int conv_dispatch(const es_conv_args* a, es_stream stream, int* emits) {
+constexpr int LDS256 = 3 * (256 * BK * 2 + BNP * BK * 2), LDS128 = 3 * (128 * BK * 2 + BNP * BK * 2), LDS64 = 3 * (64 * BK * 2 + BNP * BK * 2);
+constexpr int LDSLIN = LDS256 + 8 * 16 * 116 * 4;            // k_linear_ws: the ring + the epilogue slabs behind it
+constexpr int LDSDEEP = 7 * (64 * BK * 2 + BNP * BK * 2);    // k_linear_deep: 7-slot ring
+constexpr int LDSWS3 = 9 * 16384;                            // k_conv_ws3: 7 B slots + 2 A slots
+
+static int conv_route(const es_conv_args* a, ConvRoute* r) {
+    *r = ConvRoute{};
     ES_REQUIRE(a->Cin % 32 == 0 && a->Cin > 0, "es_conv_mfma_f16: Cin=%d must be a positive multiple of 32", a->Cin);
     ES_REQUIRE(a->taps == 27 || a->taps == 1, "es_conv_mfma_f16: taps=%d", a->taps);
     ES_REQUIRE(!a->a2 || (a->Cin2 % 32 == 0 && a->Cin2 > 0), "es_conv_mfma_f16: Cin2=%d", a->Cin2);
@@ -2905,7 +2882,7 @@ static int conv_dispatch(const es_conv_args* a, es_stream stream, int* emits) {
     ES_REQUIRE(a->epilogue == ES_EPI_NONE || (a->epilogue == ES_EPI_GEGLU && a->N % 224 == 0 && a->out_f16 && !a->out_f32 && !a->res &&
                                               !a->rowvec && !a->a2 && a->bias && a->out_ld >= a->N / 2 && a->out_ld % 8 == 0 && a->splitk <= 1),
                "es_conv_mfma_f16: GEGLU epilogue needs N %% 224 == 0 (N=%d), bias, f16 output only, no split-K", a->N);
-    ConvGeom g;
+    ConvGeom& g = r->g;
     g.O = a->O; g.D = a->D; g.H = a->H; g.W = a->W;
     g.Hi = a->H; g.Wi = a->W;
     g.Di = a->D;
@@ -2916,9 +2893,9 @@ static int conv_dispatch(const es_conv_args* a, es_stream stream, int* emits) {
     if (a->mode == ES_CONV_UP_HW || a->mode == ES_CONV_UP_DHW) { g.Hi = a->H / 2; g.Wi = a->W / 2; }
     g.lw = ilog2_exact(a->W); g.lh = ilog2_exact(a->H); g.ld = ilog2_exact(a->D);
     ES_REQUIRE(g.lw >= 0 && g.lh >= 0 && g.ld >= 0, "es_conv_mfma_f16: D,H,W must be powers of two (%d,%d,%d)", a->D, a->H, a->W);
-    int ncdhw = a->out_ld < 0 ? 1 : 0;            // out_ld < 0 selects NCDHW fp32 output [O,N,V]
+    const int ncdhw = r->ncdhw = a->out_ld < 0 ? 1 : 0;            // out_ld < 0 selects NCDHW fp32 output [O,N,V]
     ES_REQUIRE(!ncdhw || (a->out_f32 && !a->res && !a->out_f16), "es_conv_mfma_f16: NCDHW output is fp32-only, no residual");
-    const long M = (long)a->O * a->D * a->H * a->W;
+    const long M = r->M = (long)a->O * a->D * a->H * a->W;
     // split-K factors are derived from Mh: the row count of the WHOLE problem when this launch is one shard of it
     // O_hint < 0 (round 6): the CANONICAL arithmetic of a reference shard of -O_hint objects, whatever the launch's own object count --
     // every rank of every world size (1 included) cuts K where a shard of that size is cut best, so all of them leave the same bits
@@ -2936,46 +2913,18 @@ static int conv_dispatch(const es_conv_args* a, es_stream stream, int* emits) {
         if (per_obj_in2 > 0) omax = std::min(omax, lim / per_obj_in2);
         ES_REQUIRE(omax >= 1, "es_conv_mfma_f16: one object exceeds 2 GiB of input (%ld bytes)", per_obj_in);
         if (omax < a->O) {
-            if (emits) {
-                // a chunked launch forms no GroupNorm sums in its epilogues; its chunks split K as launches of omax objects do (with
-                // O_hint: as the whole / the reference problem does) and write their slabs into the SAME workspace: report the slab
-                // count in units of the whole launch's M x N (es_conv_split_of: the planner sizes the workspace with it)
-                es_conv_args c = *a;
-                c.O = (int32_t)omax;
-                c.O_hint = a->O_hint < 0 ? a->O_hint : (a->O_hint > a->O ? a->O_hint : a->O);
-                c.gn_stats_out = nullptr; c.gn_part_out = nullptr;
-                int e2 = 0;
-                if (int rc = conv_dispatch(&c, nullptr, &e2)) return rc;
-                const long sc = e2 >> 8;
-                *emits = (int)((sc * omax + a->O - 1) / a->O) << 8;
-                return 0;
-            }
-            const long V = (long)a->D * a->H * a->W;
-            for (long o0 = 0; o0 < a->O; o0 += omax) {
-                es_conv_args c = *a;
-                c.O = (int32_t)std::min(omax, (long)a->O - o0);
-                c.O_hint = a->O_hint < 0 ? a->O_hint : (a->O_hint > a->O ? a->O_hint : a->O);
-                c.a = (const char*)a->a + o0 * per_obj_in;
-                if (a->a2) c.a2 = (const char*)a->a2 + o0 * per_obj_in2;
-                if (a->rowvec) c.rowvec = a->rowvec + o0 * a->rowvec_ld;
-                if (ncdhw) {
-                    c.out_f32 = a->out_f32 + o0 * a->N * V;
-                } else {
-                    if (a->res) c.res = a->res + o0 * V * a->out_ld;
-                    if (a->out_f32) c.out_f32 = a->out_f32 + o0 * V * a->out_ld;
-                    if (a->out_f16) c.out_f16 = (char*)a->out_f16 + o0 * V * a->out_ld * 2;
-                }
-                c.gn_stats_out = nullptr;                  // (the planes are laid out for the whole tensor: one pass below)
-                c.gn_part_out = nullptr;                   // (never requested: es_conv_emits_gn_part() == 0 for a chunked launch)
-                if (int rc = conv_dispatch(&c, stream, nullptr)) return rc;
-            }
-            if (a->gn_stats_out) {
-                ES_REQUIRE(a->out_f32 && !ncdhw && a->N % 4 == 0 && a->out_ld % 4 == 0 && V % 64 == 0, "es_conv_mfma_f16: gn_stats_out needs a channels-last fp32 output");
-                const long Mt = (long)a->O * V, n4 = ((Mt + 63) / 64) * (a->N / 4);
-                const int blocks = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
-                hipLaunchKernelGGL(k_rowgroup_stats, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const float*)a->out_f32, Mt, a->N, a->out_ld, a->gn_stats_out);
-                ES_CHECK_HIP(hipGetLastError());
-            }
+            // a chunked launch forms no GroupNorm sums in its epilogues; its chunks split K as launches of omax objects do (with
+            // O_hint: as the whole / the reference problem does) and write their slabs into the SAME workspace: report the slab
+            // count in units of the whole launch's M x N (es_conv_split_of: the planner sizes the workspace with it)
+            es_conv_args c = *a;
+            c.O = (int32_t)omax;
+            c.O_hint = a->O_hint < 0 ? a->O_hint : (a->O_hint > a->O ? a->O_hint : a->O);
+            c.gn_stats_out = nullptr; c.gn_part_out = nullptr;
+            ConvRoute rc;
+            if (int err = conv_route(&c, &rc)) return err;
+            r->omax = omax;
+            r->slabs = (int)((rc.slabs * omax + a->O - 1) / a->O);
+            r->stats_pass = a->gn_stats_out != nullptr;        // (the planes are laid out for the whole tensor: one pass behind the chunks)
             return 0;
         }
     }
@@ -2983,22 +2932,12 @@ static int conv_dispatch(const es_conv_args* a, es_stream stream, int* emits) {
     // inputs (UNet eps conv 224 -> 3) go through the MFMA tile: 98 % column padding, but the direct kernel's 756
     // dependent 16-B loads per voxel cost 2.4x (O=32) to 10x (O=4) more than the padded tile.
     if (a->N <= 4 && a->taps == 27 && a->Cin <= 64) {
-        if (emits) { *emits = 0; return 0; }
-        ES_REQUIRE(a->mode == ES_CONV_SAME && !a->a2 && !a->res && !a->rowvec && !a->out_f16 && !a->gn_stats_out,
-                   "es_conv_mfma_f16: the N<=4, Cin<=64 direct kernel takes SAME mode, fp32 output, no fusions");
         const size_t lds_t = (size_t)1000 * (a->Cin * 2 + 16) + (size_t)a->N * 27 * a->Cin * 2;
-        if (a->D % 8 == 0 && a->H % 8 == 0 && a->W % 8 == 0 && a->Cin % 8 == 0 && lds_t <= 160 * 1024) {
-            static std::once_flag once_t;
-            static hipError_t attr_t = hipSuccess;
-            std::call_once(once_t, [] { attr_t = hipFuncSetAttribute((const void*)k_conv_small_n_tiled, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-            ES_REQUIRE(attr_t == hipSuccess, "es_conv_mfma_f16: hipFuncSetAttribute failed: %s", hipGetErrorString(attr_t));
-            const unsigned nblk = (unsigned)((long)a->O * (a->D / 8) * (a->H / 8) * (a->W / 8));
-            hipLaunchKernelGGL(k_conv_small_n_tiled, dim3(nblk), dim3(256), lds_t, (hipStream_t)stream, *a, g, ncdhw);
-        } else {
-            hipLaunchKernelGGL(k_conv_small_n, dim3((unsigned)((M + 255) / 256)), dim3(256), (size_t)a->N * 27 * a->Cin * 2,
-                               (hipStream_t)stream, *a, g, ncdhw);
-        }
-        ES_CHECK_HIP(hipGetLastError());
+        const bool tiled = a->D % 8 == 0 && a->H % 8 == 0 && a->W % 8 == 0 && a->Cin % 8 == 0 && lds_t <= 160 * 1024;
+        r->kernel = tiled ? ConvKernel::small_n_tiled : ConvKernel::small_n;
+        r->grid = dim3((unsigned)(tiled ? (long)a->O * (a->D / 8) * (a->H / 8) * (a->W / 8) : (M + 255) / 256));
+        r->lds = tiled ? lds_t : (size_t)a->N * 27 * a->Cin * 2;
+        r->S = 1;
         return 0;
     }
     // N <= 16 from a wide input, NCDHW fp32 output, no fusions (the UNet's output conv): halo'd LDS image + one MFMA column
@@ -3006,14 +2945,9 @@ static int conv_dispatch(const es_conv_args* a, es_stream stream, int* emits) {
     if (a->N <= 16 && a->taps == 27 && a->Cin > 64 && ncdhw && a->mode == ES_CONV_SAME && !a->a2 && !a->res && !a->rowvec &&
         !a->out_f16 && a->D % 4 == 0 && a->H % 4 == 0 && a->W % 16 == 0 && !(n16_env && atoi(n16_env) == 0) &&
         (long)a->O * a->D * a->H * a->W * a->Cin * 2 < (1L << 31)) {
-        if (emits) { *emits = 0; return 0; }
-        static std::once_flag once_n;
-        static hipError_t attr_n = hipSuccess;
-        std::call_once(once_n, [] { attr_n = hipFuncSetAttribute((const void*)k_conv_n16, hipFuncAttributeMaxDynamicSharedMemorySize, N16_A_BYTES + N16_B_BYTES); });
-        ES_REQUIRE(attr_n == hipSuccess, "es_conv_mfma_f16: hipFuncSetAttribute failed: %s", hipGetErrorString(attr_n));
-        const unsigned nblk = (unsigned)((long)a->O * (a->D / 4) * (a->H / 4) * (a->W / 16));
-        hipLaunchKernelGGL(k_conv_n16, dim3(nblk), dim3(256), N16_A_BYTES + N16_B_BYTES, (hipStream_t)stream, *a, g);
-        ES_CHECK_HIP(hipGetLastError());
+        r->kernel = ConvKernel::n16;
+        r->grid = dim3((unsigned)((long)a->O * (a->D / 4) * (a->H / 4) * (a->W / 16)));
+        r->S = 1;
         return 0;
     }
     const int ntn = (a->N + BN - 1) / BN;
@@ -3025,12 +2959,7 @@ static int conv_dispatch(const es_conv_args* a, es_stream stream, int* emits) {
     const long wg256 = ((M + 255) / 256) * ntn, wg128 = ((M + 127) / 128) * ntn;
     const long hg256 = ((Mh + 255) / 256) * ntn, hg128 = ((Mh + 127) / 128) * ntn;      // the same counts for the whole problem
     const int nks = a->taps * (a->Cin / 32) + (a->a2 ? a->Cin2 / 32 : 0);
-    constexpr int LDSLIN_GEGLU = 4 * (256 * BK * 2 + BNP * BK * 2) + 8 * 16 * 72 * 2;      // k_linear_ws<GEGLU>: 4-slot ring + fp16 slabs
-    constexpr int LDS256 = 3 * (256 * BK * 2 + BNP * BK * 2), LDS128 = 3 * (128 * BK * 2 + BNP * BK * 2),
-                  LDS64 = 3 * (64 * BK * 2 + BNP * BK * 2);
-    hipStream_t st = (hipStream_t)stream;
     const bool want_stats = a->gn_stats_out != nullptr;
-    bool stats_done = false;
     ES_REQUIRE(!want_stats || ((a->out_f32 || a->out_f16) && !ncdhw && a->N % 4 == 0 && a->out_ld % 4 == 0 && (a->D * a->H * a->W) % 64 == 0 &&
                                a->epilogue == ES_EPI_NONE),
                "es_conv_mfma_f16: gn_stats_out needs a channels-last output, N %% 4 == 0 and voxels per object %% 64 == 0");
@@ -3166,177 +3095,255 @@ static int conv_dispatch(const es_conv_args* a, es_stream stream, int* emits) {
     int ncb = 1;
     if (route256 && ws && a->taps == 1 && !a->a2 && a->mode == ES_CONV_SAME && S == 1 && ntn >= 2 && !(lin_env && atoi(lin_env) == 0)) {
         static const int cand[5] = {8, 6, 4, 3, 2};
-        static const char* ncb_env = getenv("ES_LIN_NCB_MAX");    // A/B switch (timing only: same K order, same bits): cap of the walk
-        const int ncb_max = ncb_env ? atoi(ncb_env) : 8;
         for (int k = 0; k < 5; ++k)
-            if (cand[k] <= ncb_max && ntn % cand[k] == 0 && ((M + 255) / 256) * (ntn / cand[k]) >= 256) { ncb = cand[k]; break; }
+            if (ntn % cand[k] == 0 && ((M + 255) / 256) * (ntn / cand[k]) >= 256) { ncb = cand[k]; break; }
     }
     // the producer/consumer 256-row kernel forms the row-group sums of gn_stats_out in its epilogue; every other route runs
     // k_rowgroup_stats over the finished output
     const bool epi_stats = (route256 || st_bm == 128 || (few_small && few_bm == 128)) && ncb == 1 && ws && !geglu && S == 1 && (a->out_f32 || a->out_f16) && a->N % 4 == 0 && a->out_ld % 4 == 0 &&
                            (a->D * a->H * a->W) % 64 == 0;
-    // (bit 1) a split launch can form the next GroupNorm's per-tile partial sums in its reduction kernel (gn_part_out)
+    // a split launch can form the next GroupNorm's per-tile partial sums in its reduction kernel (gn_part_out)
     // (the few-objects routes: from the REFERENCE problem's decision -- K streams inside the workgroup have no reduction launch,
     //  whatever kernel realises the split in this launch)
     const bool part_ok = S > 1 && !deep && few_ref != 2 && a->out_f32 && !ncdhw && a->N % 4 == 0 && a->N <= 2048 && a->out_ld == a->N && a->gn_part_groups > 0 &&
                          a->gn_part_groups <= 64 && a->N % a->gn_part_groups == 0;
-    if (emits) { *emits = (epi_stats ? 1 : 0) | (part_ok ? 2 : 0) | ((few_kw ? 1 : S) << 8); return 0; }
-    {   // one-off per process, thread-safe: dynamic LDS limits of the conv kernels
-        static std::once_flag once;
-        static hipError_t attr_err = hipSuccess;
-        std::call_once(once, [] {
-            auto set = [](const void* f, int bytes) {
-                const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-                if (e != hipSuccess && attr_err == hipSuccess) attr_err = e;
-            };
-            set((const void*)k_conv_lean<256, 8>, LDS256);
-            set((const void*)k_conv_lean<128, 4>, LDS128);
-            set((const void*)k_conv_lean<64, 4>, LDS64);
-            set((const void*)k_conv_lean<256, 8, true>, LDS256);
-            set((const void*)k_conv_lean<128, 4, true>, LDS128);
-            set((const void*)k_conv_lean<64, 4, true>, LDS64);
-            set((const void*)k_linear_deep, 7 * (64 * BK * 2 + BNP * BK * 2));
-            set((const void*)k_linear_ws<ES_EPI_NONE>, LDS256 + 8 * 16 * 116 * 4);
-            set((const void*)k_linear_ws<ES_EPI_GEGLU>, LDS256 + 8 * 16 * 116 * 4);
-            set((const void*)k_linear_ws<ES_EPI_GEGLU, 4>, LDSLIN_GEGLU);
-        });
-        ES_REQUIRE(attr_err == hipSuccess, "es_conv_mfma_f16: hipFuncSetAttribute failed: %s", hipGetErrorString(attr_err));
-    }
+    r->upm = upm; r->geglu = geglu; r->ncb = ncb;
+    r->epi_stats = epi_stats; r->part_ok = part_ok;
+    r->stats = want_stats && epi_stats;
+    r->stats_pass = want_stats && !epi_stats;      // (every kernel chosen below under epi_stats has the epilogue that forms the sums)
+    r->slabs = few_kw ? 1 : S;
+    // ---- the kernel that realises the decision, and its grid ------------------------------------------------------------------------
+    const unsigned uy = (unsigned)ntn;
     if (few_kw) {
-        if (int rc = launch_kw<4, 1>(a, g, ncdhw, M, ntn, 1, st, upm, geglu)) return rc;
-        S = 1;                                                 // (the four K ranges met in LDS: no slabs, no reduction launch)
+        S = 1;                                                 // (the four K ranges meet in LDS: no slabs, no reduction launch)
+        r->kernel = ConvKernel::kw_4_1;
+        r->grid = dim3((unsigned)((M + 63) / 64), 2 * uy, 1);
     } else if (few_small) {
-        const dim3 grid((unsigned)((M + few_bm - 1) / few_bm), ntn, S);
-        const bool stt = want_stats && epi_stats;
-        int rc;
-        if (few_bm == 64) rc = launch_ws<64, 4, 4, 3>(a, g, ncdhw, grid, st, upm, geglu, stt);
-        else rc = launch_ws<128, 4, 8, 5>(a, g, ncdhw, grid, st, upm, geglu, stt);
-        if (rc) return rc;
-        stats_done = stt;
+        r->kernel = few_bm == 64 ? ConvKernel::ws_64_4_4_3 : ConvKernel::ws_128_4_8_5;
+        r->grid = dim3((unsigned)((M + few_bm - 1) / few_bm), uy, S);
     } else if (kw_ks) {
-        int rc = 1;
-        if (kw_ks == 4) rc = launch_kw<4, 1>(a, g, ncdhw, M, ntn, S, st, upm, geglu);
-        else if (kw_ks == 2) rc = launch_kw<2, 2>(a, g, ncdhw, M, ntn, S, st, upm, geglu);
-        else ES_REQUIRE(false, "es_conv_mfma_f16: conv_kw_ks=%d (2 or 4)", kw_ks);
-        if (rc) return rc;
+        r->kernel = kw_ks == 4 ? ConvKernel::kw_4_1 : kw_ks == 2 ? ConvKernel::kw_2_2 : ConvKernel::none;
+        snprintf(r->unbuilt, sizeof(r->unbuilt), "conv_kw_ks=%d (2 or 4)", kw_ks);
+        r->grid = dim3((unsigned)((M + 63) / 64), kw_ks == 4 ? 2 * uy : uy, S);
     } else if (st_bm) {
-        const int np = vo("conv_st_np");
-        const dim3 grid((unsigned)((M + st_bm - 1) / st_bm), ntn, S);
-        const bool stt = want_stats && epi_stats;
-        int rc = 1;
-        const int ns = vo("conv_st_ns");
-        if (st_bm == 64 && np == 4 && ns == 3) rc = launch_ws<64, 4, 4, 3>(a, g, ncdhw, grid, st, upm, geglu, stt);
-        else if (st_bm == 64 && np == 4 && ns == 6) rc = launch_ws<64, 4, 4, 6>(a, g, ncdhw, grid, st, upm, geglu, stt);
-        else if (st_bm == 128 && np == 4 && ns == 3) rc = launch_ws<128, 4, 4, 3>(a, g, ncdhw, grid, st, upm, geglu, stt);
-        else if (st_bm == 128 && np == 8 && ns == 3) rc = launch_ws<128, 4, 8, 3>(a, g, ncdhw, grid, st, upm, geglu, stt);
-        else if (st_bm == 128 && np == 8 && ns == 5) rc = launch_ws<128, 4, 8, 5>(a, g, ncdhw, grid, st, upm, geglu, stt);
-        else ES_REQUIRE(false, "es_conv_mfma_f16: conv_st_bm=%d conv_st_np=%d conv_st_ns=%d is not a built tile", st_bm, np, ns);
-        if (rc) return rc;
-        stats_done = stt;
+        const int np = vo("conv_st_np"), ns = vo("conv_st_ns");
+        if (st_bm == 64 && np == 4 && ns == 3) r->kernel = ConvKernel::ws_64_4_4_3;
+        else if (st_bm == 64 && np == 4 && ns == 6) r->kernel = ConvKernel::ws_64_4_4_6;
+        else if (st_bm == 128 && np == 4 && ns == 3) r->kernel = ConvKernel::ws_128_4_4_3;
+        else if (st_bm == 128 && np == 8 && ns == 3) r->kernel = ConvKernel::ws_128_4_8_3;
+        else if (st_bm == 128 && np == 8 && ns == 5) r->kernel = ConvKernel::ws_128_4_8_5;
+        else snprintf(r->unbuilt, sizeof(r->unbuilt), "conv_st_bm=%d conv_st_np=%d conv_st_ns=%d is not a built tile", st_bm, np, ns);
+        r->grid = dim3((unsigned)((M + st_bm - 1) / st_bm), uy, S);
     } else if (deep) {
         S = 1;
-        hipLaunchKernelGGL(k_linear_deep, dim3((unsigned)((M + 63) / 64), ntn, 1), dim3(256), 7 * (64 * BK * 2 + BNP * BK * 2), st, *a, g);
+        r->kernel = ConvKernel::linear_deep;
+        r->grid = dim3((unsigned)((M + 63) / 64), uy, 1);
     } else if (route256) {
-        dim3 grid((unsigned)((M + 255) / 256), ntn, S);
+        r->grid = dim3((unsigned)((M + 255) / 256), uy, S);
         if (ncb > 1) {
-            const dim3 lgrid(grid.x, (unsigned)(ntn / ncb), 1);
-            constexpr int LDSLIN = LDS256 + 8 * 16 * 116 * 4;
-            // (a FOURTH ring slot fits behind the GEGLU variant's small fp16 slabs -- the step DESIGN.md had listed as cheap since round 2;
-            //  measured in round 4 on one box: shape step 18.41 ms with three slots, 18.44-18.47 with four: no gain, kept as a switch)
-            static const char* ring_env = getenv("ES_LIN_RING");      // A/B switch (timing only): 4 = four-slot ring for the GEGLU variant
-            if (geglu && ring_env && atoi(ring_env) == 4) hipLaunchKernelGGL((k_linear_ws<ES_EPI_GEGLU, 4>), lgrid, dim3(768), LDSLIN_GEGLU, st, *a, g, ncb);
-            else if (geglu) hipLaunchKernelGGL((k_linear_ws<ES_EPI_GEGLU>), lgrid, dim3(768), LDSLIN, st, *a, g, ncb);
-            else hipLaunchKernelGGL((k_linear_ws<ES_EPI_NONE>), lgrid, dim3(768), LDSLIN, st, *a, g, ncb);
+            r->kernel = ConvKernel::linear_ws;
+            r->grid = dim3(r->grid.x, (unsigned)(ntn / ncb), 1);
         } else if (ws && (!geglu || !upm)) {
-            // ring depth of the 256-row tile: 3 (rounds 1-5); ES_CONV_NS = 4 / 5 is a timing-only A/B switch (same K order, same bits)
-            static const char* ns_env = getenv("ES_CONV_NS");
-            const int ns = ns_env ? atoi(ns_env) : 3;
-            const bool stt = want_stats && epi_stats;
             // 3x3x3 SAME convs on volumes with W <= 16: the A tile of a (chunk, kd, kh) group staged once, the kw = -1 / +1 operands
             // shifted in registers (k_conv_ws3; bit-identical to k_conv_ws).  ES_CONV_A3 = 0 / 1: timing-only A/B switch
             static const char* a3_env = getenv("ES_CONV_A3");
             const bool a3 = (a3_env ? atoi(a3_env) != 0 : ES_CONV_A3_DEFAULT) && a->taps == 27 && a->mode == ES_CONV_SAME && !a->a2 && a->W <= 16 && a->W >= 4;
-            if (a3) {
-                static std::once_flag once3;
-                static hipError_t err3 = hipSuccess;
-                std::call_once(once3, [] {
-                    err3 = hipFuncSetAttribute((const void*)k_conv_ws3<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 6 * 16384);
-                    for (auto fl : {std::pair<const void*, int>{(const void*)k_conv_ws3<true>, 6 * 16384}, {(const void*)k_conv_ws3<false, true>, 9 * 16384},
-                                    {(const void*)k_conv_ws3<true, true>, 9 * 16384}}) {
-                        const hipError_t e2 = hipFuncSetAttribute(fl.first, hipFuncAttributeMaxDynamicSharedMemorySize, fl.second);
-                        if (err3 == hipSuccess) err3 = e2;
-                    }
-                });
-                static const char* gb_env = getenv("ES_CONV_GB");          // timing-only A/B switch: 0 = one barrier per K unit instead of one per (chunk, kd, kh) group
-                ES_REQUIRE(err3 == hipSuccess, "es_conv_mfma_f16: hipFuncSetAttribute failed: %s", hipGetErrorString(err3));
-                if (!gb_env || atoi(gb_env) != 0) {
-                    if (stt) hipLaunchKernelGGL((k_conv_ws3<true, true>), grid, dim3(768), 9 * 16384, st, *a, g);
-                    else hipLaunchKernelGGL((k_conv_ws3<false, true>), grid, dim3(768), 9 * 16384, st, *a, g);
-                }
-                else if (stt) hipLaunchKernelGGL((k_conv_ws3<true>), grid, dim3(768), 6 * 16384, st, *a, g);
-                else hipLaunchKernelGGL((k_conv_ws3<false>), grid, dim3(768), 6 * 16384, st, *a, g);
-                if (stt) stats_done = true;
-            } else {
-            int rc;
-            if (ns == 4) rc = launch_ws<256, 8, 4, 4>(a, g, ncdhw, grid, st, upm, geglu, stt);
-            else if (ns == 5) rc = launch_ws<256, 8, 4, 5>(a, g, ncdhw, grid, st, upm, geglu, stt);
-            else rc = launch_ws<256, 8, 4, 3>(a, g, ncdhw, grid, st, upm, geglu, stt);
-            if (rc) return rc;
-            if (stt) stats_done = true;
-            }
-        }
-        else if (upm) hipLaunchKernelGGL((k_conv_lean<256, 8, true>), grid, dim3(512), LDS256, st, *a, g, ncdhw);
-        else hipLaunchKernelGGL((k_conv_lean<256, 8>), grid, dim3(512), LDS256, st, *a, g, ncdhw);
-    } else if ((wg128 >= 512 || S > 1) && !tiny_split) {
-        dim3 grid((unsigned)((M + 127) / 128), ntn, S);
-        if (upm) hipLaunchKernelGGL((k_conv_lean<128, 4, true>), grid, dim3(256), LDS128, st, *a, g, ncdhw);
-        else hipLaunchKernelGGL((k_conv_lean<128, 4>), grid, dim3(256), LDS128, st, *a, g, ncdhw);
-    } else {
-        dim3 grid((unsigned)((M + 63) / 64), ntn, tiny_split ? S : 1);
-        if (upm) hipLaunchKernelGGL((k_conv_lean<64, 4, true>), grid, dim3(256), LDS64, st, *a, g, ncdhw);
-        else hipLaunchKernelGGL((k_conv_lean<64, 4>), grid, dim3(256), LDS64, st, *a, g, ncdhw);
-    }
-    if (S > 1) {
-        const long n4 = M * (a->N / 4);
-        const int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
-        if (a->gn_part_out && part_ok) {
-            const int V = a->D * a->H * a->W;
-            const int vt = gn_voxel_tile(Oh, V);
-            hipLaunchKernelGGL(k_conv_splitk_reduce_gn, dim3((V + vt - 1) / vt, a->O), dim3(256), 0, st, *a, M, V, S, vt);
+            r->kernel = a3 ? ConvKernel::ws3 : ConvKernel::ws_256_8_4_3;
         } else
-            hipLaunchKernelGGL(k_conv_splitk_reduce, dim3(blocks), dim3(256), 0, st, *a, M, a->D * a->H * a->W, S);
+            r->kernel = ConvKernel::lean_256;
+    } else if ((wg128 >= 512 || S > 1) && !tiny_split) {
+        r->kernel = ConvKernel::lean_128;
+        r->grid = dim3((unsigned)((M + 127) / 128), uy, S);
+    } else {
+        r->kernel = ConvKernel::lean_64;
+        r->grid = dim3((unsigned)((M + 63) / 64), uy, tiny_split ? S : 1);
     }
-    if (want_stats && !stats_done) {
+    r->S = S;
+    if (S > 1) {
+        r->reduce = a->gn_part_out && part_ok ? ConvReduce::gn_part : ConvReduce::plain;
+        if (r->reduce == ConvReduce::gn_part) r->vt = gn_voxel_tile(Oh, a->D * a->H * a->W);
+    }
+    return 0;
+}
+
+// k_conv_ws launcher for one (tile rows, consumer waves, producer waves, ring depth): the 256-row tile of rounds 1-5 (8 consumers as
+// 4 x 2, 4 producers) and, round 6, the few-objects tiles of 64 / 128 rows (4 consumers as 2 x 2 of BM_/2 x 112, 4 or 8 producers,
+// deeper rings).
+template <int BM_, int NC_, int NP_, int NS_>
+static int launch_ws(const es_conv_args* a, const ConvRoute& r, hipStream_t st) {
+    constexpr int LDS = NS_ * (BM_ * BK * 2 + BNP * BK * 2);
+    constexpr bool CAN_STATS = BM_ / (NC_ / 2) == 64;             // row-group sums are per 64-row wave
+    static_assert(LDS <= 160 * 1024, "ring exceeds the CU's LDS");
+    static const LdsLimits lim{{(const void*)k_conv_ws<BM_, NC_, NP_, false, ES_EPI_NONE, false, NS_>, LDS},
+                               {(const void*)k_conv_ws<BM_, NC_, NP_, true, ES_EPI_NONE, false, NS_>, LDS},
+                               {(const void*)k_conv_ws<BM_, NC_, NP_, false, ES_EPI_GEGLU, false, NS_>, LDS}};
+    ES_REQUIRE(lim.err == hipSuccess, "es_conv_mfma_f16: hipFuncSetAttribute failed: %s", hipGetErrorString(lim.err));
+    const dim3 blk(64 * (NC_ + NP_));
+    if (r.geglu) hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, false, ES_EPI_GEGLU, false, NS_>), r.grid, blk, LDS, st, *a, r.g, r.ncdhw);
+    else if (r.stats) {
+        if constexpr (CAN_STATS) {
+            static const LdsLimits lim_stats{{(const void*)k_conv_ws<BM_, NC_, NP_, false, ES_EPI_NONE, true, NS_>, LDS},
+                                             {(const void*)k_conv_ws<BM_, NC_, NP_, true, ES_EPI_NONE, true, NS_>, LDS}};
+            ES_REQUIRE(lim_stats.err == hipSuccess, "es_conv_mfma_f16: hipFuncSetAttribute failed: %s", hipGetErrorString(lim_stats.err));
+            if (r.upm) hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, true, ES_EPI_NONE, true, NS_>), r.grid, blk, LDS, st, *a, r.g, r.ncdhw);
+            else hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, false, ES_EPI_NONE, true, NS_>), r.grid, blk, LDS, st, *a, r.g, r.ncdhw);
+        } else ES_REQUIRE(false, "launch_ws: row-group sums need 64-row waves");
+    }
+    else if (r.upm) hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, true, ES_EPI_NONE, false, NS_>), r.grid, blk, LDS, st, *a, r.g, r.ncdhw);
+    else hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, false, ES_EPI_NONE, false, NS_>), r.grid, blk, LDS, st, *a, r.g, r.ncdhw);
+    return 0;
+}
+
+// k_conv_kw: K split inside the workgroup (KS_ streams x NCH_ column halves of 112)
+template <int KS_, int NCH_>
+static int launch_kw(const es_conv_args* a, const ConvRoute& r, hipStream_t st) {
+    constexpr int RING = 3 * KS_ * (64 * BK * 2 + NCH_ * 112 * BK * 2), PART = 4 * 112 * 64 * 4;
+    constexpr int LDS = RING > PART ? RING : PART;
+    static const LdsLimits lim{{(const void*)k_conv_kw<KS_, NCH_, false, ES_EPI_NONE>, LDS},
+                               {(const void*)k_conv_kw<KS_, NCH_, true, ES_EPI_NONE>, LDS},
+                               {(const void*)k_conv_kw<KS_, NCH_, false, ES_EPI_GEGLU>, LDS}};
+    ES_REQUIRE(lim.err == hipSuccess, "es_conv_mfma_f16: hipFuncSetAttribute failed: %s", hipGetErrorString(lim.err));
+    const dim3 blk(768);
+    if (r.geglu) hipLaunchKernelGGL((k_conv_kw<KS_, NCH_, false, ES_EPI_GEGLU>), r.grid, blk, LDS, st, *a, r.g, r.ncdhw);
+    else if (r.upm) hipLaunchKernelGGL((k_conv_kw<KS_, NCH_, true, ES_EPI_NONE>), r.grid, blk, LDS, st, *a, r.g, r.ncdhw);
+    else hipLaunchKernelGGL((k_conv_kw<KS_, NCH_, false, ES_EPI_NONE>), r.grid, blk, LDS, st, *a, r.g, r.ncdhw);
+    return 0;
+}
+
+// k_conv_lean: the non-specialised tiles of BM_ rows, NW_ waves
+template <int BM_, int NW_>
+static void launch_lean(const es_conv_args* a, const ConvRoute& r, hipStream_t st) {
+    constexpr int LDS = 3 * (BM_ * BK * 2 + BNP * BK * 2);
+    if (r.upm) hipLaunchKernelGGL((k_conv_lean<BM_, NW_, true>), r.grid, dim3(64 * NW_), LDS, st, *a, r.g, r.ncdhw);
+    else hipLaunchKernelGGL((k_conv_lean<BM_, NW_>), r.grid, dim3(64 * NW_), LDS, st, *a, r.g, r.ncdhw);
+}
+
+// Row-group sums of gn_stats_out by a pass over the finished fp32 output of `rows` rows
+static void launch_rowgroup_stats(const es_conv_args* a, long rows, hipStream_t st) {
+    const long n4 = ((rows + 63) / 64) * (a->N / 4);
+    const int blocks = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
+    hipLaunchKernelGGL(k_rowgroup_stats, dim3(blocks), dim3(256), 0, st, (const float*)a->out_f32, rows, a->N, a->out_ld, a->gn_stats_out);
+}
+
+// Launches what the route names: its kernel, then the reduction and the statistics pass it asks for.  Nothing is decided here.
+static int conv_launch(const es_conv_args* a, const ConvRoute& r, hipStream_t st) {
+    static const LdsLimits lim{{(const void*)k_conv_small_n_tiled, 160 * 1024},
+                               {(const void*)k_conv_n16, N16_A_BYTES + N16_B_BYTES},
+                               {(const void*)k_conv_lean<256, 8>, LDS256}, {(const void*)k_conv_lean<256, 8, true>, LDS256},
+                               {(const void*)k_conv_lean<128, 4>, LDS128}, {(const void*)k_conv_lean<128, 4, true>, LDS128},
+                               {(const void*)k_conv_lean<64, 4>, LDS64}, {(const void*)k_conv_lean<64, 4, true>, LDS64},
+                               {(const void*)k_linear_deep, LDSDEEP},
+                               {(const void*)k_linear_ws<ES_EPI_NONE>, LDSLIN}, {(const void*)k_linear_ws<ES_EPI_GEGLU>, LDSLIN},
+                               {(const void*)k_conv_ws3<false>, LDSWS3}, {(const void*)k_conv_ws3<true>, LDSWS3}};
+    ES_REQUIRE(lim.err == hipSuccess, "es_conv_mfma_f16: hipFuncSetAttribute failed: %s", hipGetErrorString(lim.err));
+    // (the queries answer for such a route; only the launch refuses it)
+    ES_REQUIRE(r.kernel != ConvKernel::none, "es_conv_mfma_f16: %s", r.omax ? "a chunked route is launched chunk by chunk" : r.unbuilt);
+    int rc = 0;
+    switch (r.kernel) {
+    case ConvKernel::none: break;
+    case ConvKernel::small_n:
+    case ConvKernel::small_n_tiled:
+        ES_REQUIRE(a->mode == ES_CONV_SAME && !a->a2 && !a->res && !a->rowvec && !a->out_f16 && !a->gn_stats_out,
+                   "es_conv_mfma_f16: the N<=4, Cin<=64 direct kernel takes SAME mode, fp32 output, no fusions");
+        if (r.kernel == ConvKernel::small_n_tiled) hipLaunchKernelGGL(k_conv_small_n_tiled, r.grid, dim3(256), r.lds, st, *a, r.g, r.ncdhw);
+        else hipLaunchKernelGGL(k_conv_small_n, r.grid, dim3(256), r.lds, st, *a, r.g, r.ncdhw);
+        break;
+    case ConvKernel::n16: hipLaunchKernelGGL(k_conv_n16, r.grid, dim3(256), N16_A_BYTES + N16_B_BYTES, st, *a, r.g); break;
+    case ConvKernel::kw_4_1: rc = launch_kw<4, 1>(a, r, st); break;
+    case ConvKernel::kw_2_2: rc = launch_kw<2, 2>(a, r, st); break;
+    case ConvKernel::ws_256_8_4_3: rc = launch_ws<256, 8, 4, 3>(a, r, st); break;
+    case ConvKernel::ws_64_4_4_3: rc = launch_ws<64, 4, 4, 3>(a, r, st); break;
+    case ConvKernel::ws_64_4_4_6: rc = launch_ws<64, 4, 4, 6>(a, r, st); break;
+    case ConvKernel::ws_128_4_4_3: rc = launch_ws<128, 4, 4, 3>(a, r, st); break;
+    case ConvKernel::ws_128_4_8_3: rc = launch_ws<128, 4, 8, 3>(a, r, st); break;
+    case ConvKernel::ws_128_4_8_5: rc = launch_ws<128, 4, 8, 5>(a, r, st); break;
+    case ConvKernel::ws3:
+        if (r.stats) hipLaunchKernelGGL((k_conv_ws3<true>), r.grid, dim3(768), LDSWS3, st, *a, r.g);
+        else hipLaunchKernelGGL((k_conv_ws3<false>), r.grid, dim3(768), LDSWS3, st, *a, r.g);
+        break;
+    case ConvKernel::linear_ws:
+        if (r.geglu) hipLaunchKernelGGL((k_linear_ws<ES_EPI_GEGLU>), r.grid, dim3(768), LDSLIN, st, *a, r.g, r.ncb);
+        else hipLaunchKernelGGL((k_linear_ws<ES_EPI_NONE>), r.grid, dim3(768), LDSLIN, st, *a, r.g, r.ncb);
+        break;
+    case ConvKernel::linear_deep: hipLaunchKernelGGL(k_linear_deep, r.grid, dim3(256), LDSDEEP, st, *a, r.g); break;
+    case ConvKernel::lean_256: launch_lean<256, 8>(a, r, st); break;
+    case ConvKernel::lean_128: launch_lean<128, 4>(a, r, st); break;
+    case ConvKernel::lean_64: launch_lean<64, 4>(a, r, st); break;
+    }
+    if (rc) return rc;
+    const int V = a->D * a->H * a->W;
+    if (r.reduce == ConvReduce::gn_part)
+        hipLaunchKernelGGL(k_conv_splitk_reduce_gn, dim3((V + r.vt - 1) / r.vt, a->O), dim3(256), 0, st, *a, r.M, V, r.S, r.vt);
+    else if (r.reduce == ConvReduce::plain) {
+        const long n4 = r.M * (a->N / 4);
+        const int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
+        hipLaunchKernelGGL(k_conv_splitk_reduce, dim3(blocks), dim3(256), 0, st, *a, r.M, V, r.S);
+    }
+    if (r.stats_pass) {
         ES_REQUIRE(a->out_f32, "es_conv_mfma_f16: this launch's route forms gn_stats_out by a pass over the fp32 output: out_f32 must be given "
                                "(es_conv_emits_gn_stats() == 0)");
-        const long n4 = ((M + 63) / 64) * (a->N / 4);
-        const int blocks = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
-        hipLaunchKernelGGL(k_rowgroup_stats, dim3(blocks), dim3(256), 0, st, (const float*)a->out_f32, M, a->N, a->out_ld, a->gn_stats_out);
+        launch_rowgroup_stats(a, r.M, st);
     }
     ES_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
-extern "C" int es_conv_mfma_f16(const es_conv_args* a, es_stream stream) { return conv_dispatch(a, stream, nullptr); }
+extern "C" int es_conv_mfma_f16(const es_conv_args* a, es_stream stream) {
+    ConvRoute r;
+    if (int rc = conv_route(a, &r)) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    if (!r.omax) return conv_launch(a, r, st);
+    // over the descriptor limit: chunks of r.omax objects, each routed and launched for itself (the last one may be smaller and pick
+    // its own tile; O_hint keeps the split-K choice of the whole problem), then one statistics pass over the whole tensor
+    const long V = (long)a->D * a->H * a->W;
+    const long per_obj_in = (long)r.g.Di * r.g.Hi * r.g.Wi * a->Cin * 2, per_obj_in2 = a->a2 ? V * a->Cin2 * 2 : 0;
+    for (long o0 = 0; o0 < a->O; o0 += r.omax) {
+        es_conv_args c = *a;
+        c.O = (int32_t)std::min(r.omax, (long)a->O - o0);
+        c.O_hint = a->O_hint < 0 ? a->O_hint : (a->O_hint > a->O ? a->O_hint : a->O);
+        c.a = (const char*)a->a + o0 * per_obj_in;
+        if (a->a2) c.a2 = (const char*)a->a2 + o0 * per_obj_in2;
+        if (a->rowvec) c.rowvec = a->rowvec + o0 * a->rowvec_ld;
+        if (r.ncdhw) {
+            c.out_f32 = a->out_f32 + o0 * a->N * V;
+        } else {
+            if (a->res) c.res = a->res + o0 * V * a->out_ld;
+            if (a->out_f32) c.out_f32 = a->out_f32 + o0 * V * a->out_ld;
+            if (a->out_f16) c.out_f16 = (char*)a->out_f16 + o0 * V * a->out_ld * 2;
+        }
+        c.gn_stats_out = c.gn_part_out = nullptr;  // (the planes are laid out for the whole tensor: one pass below; partials: never asked for)
+        ConvRoute rc;
+        if (int err = conv_route(&c, &rc)) return err;
+        if (int err = conv_launch(&c, rc, st)) return err;
+    }
+    if (r.stats_pass) {
+        ES_REQUIRE(a->out_f32 && !r.ncdhw && a->N % 4 == 0 && a->out_ld % 4 == 0 && V % 64 == 0, "es_conv_mfma_f16: gn_stats_out needs a channels-last fp32 output");
+        launch_rowgroup_stats(a, r.M, st);
+        ES_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+}
 
 // 1 when es_conv_mfma_f16(args) would form gn_stats_out inside its own epilogue (the planner only asks a conv for the sums then:
 // behind any other route they would cost a pass over the output, i.e. what the GroupNorm's own statistics pass costs), 0 when
 // not, -1 on invalid arguments.  Host-only: launches nothing.
 extern "C" int es_conv_emits_gn_stats(const es_conv_args* a) {
-    int e = 0;
-    return conv_dispatch(a, nullptr, &e) == 0 ? (e & 1) : -1;
+    ConvRoute r;
+    return conv_route(a, &r) == 0 ? (int)r.epi_stats : -1;
 }
 
+// 1 when a split launch's reduction kernel can form the next GroupNorm's per-tile partial sums (gn_part_out), 0 when not, -1 on
+// invalid arguments.  Host-only.
 extern "C" int es_conv_emits_gn_part(const es_conv_args* a) {
-    int e = 0;
-    return conv_dispatch(a, nullptr, &e) == 0 ? ((e >> 1) & 1) : -1;
+    ConvRoute r;
+    return conv_route(a, &r) == 0 ? (int)r.part_ok : -1;
 }
 
 // The number of fp32 slabs [S][M][N] es_conv_mfma_f16(args) writes into args->workspace (1: none -- no split, or K split inside the
 // workgroup), -1 on invalid arguments.  Host-only: the planner sizes the workspace with it.
 extern "C" int es_conv_split_of(const es_conv_args* a) {
-    int e = 0;
-    return conv_dispatch(a, nullptr, &e) == 0 ? (e >> 8) : -1;
+    ConvRoute r;
+    return conv_route(a, &r) == 0 ? r.slabs : -1;
 }
 
 extern "C" int es_groupnorm_vol(const es_gn_args* a, es_stream stream) {
@@ -3437,12 +3444,8 @@ extern "C" int es_shape_stem(const es_stem_args* a, es_stream stream) {
     ES_REQUIRE(Cx >= 1 && Cx <= 4, "es_shape_stem: Cin=%d (3 or 4)", Cx);
     (void)n1;
     hipLaunchKernelGGL(k_stem1, dim3(64, a->O), dim3(256), (size_t)(Cx * 288 + 32 * Cx * 27) * 4, (hipStream_t)stream, *a);
-    {
-        static std::once_flag once_s;
-        static hipError_t attr_s = hipSuccess;
-        std::call_once(once_s, [] { attr_s = hipFuncSetAttribute((const void*)k_stem2, hipFuncAttributeMaxDynamicSharedMemorySize, 32 * 513 * 4); });
-        ES_REQUIRE(attr_s == hipSuccess, "es_shape_stem: hipFuncSetAttribute failed: %s", hipGetErrorString(attr_s));
-    }
+    static const LdsLimits lim{{(const void*)k_stem2, 32 * 513 * 4}};
+    ES_REQUIRE(lim.err == hipSuccess, "es_shape_stem: hipFuncSetAttribute failed: %s", hipGetErrorString(lim.err));
     hipLaunchKernelGGL(k_stem2, dim3((unsigned)((n2 * 8 + 255) / 256)), dim3(256), 32 * 513 * 4, (hipStream_t)stream, *a);
     ES_CHECK_HIP(hipGetLastError());
     return 0;
@@ -3451,14 +3454,8 @@ extern "C" int es_shape_stem(const es_stem_args* a, es_stream stream) {
 extern "C" int es_vq_lookup(const es_vq_args* a, es_stream stream) {
     ES_REQUIRE(a->n_embed > 0 && a->n_embed * 16 <= 160 * 1024 - 1024, "es_vq_lookup: n_embed=%d too large for LDS", a->n_embed);
     ES_REQUIRE(a->Cpad >= 3, "es_vq_lookup: Cpad=%d", a->Cpad);
-    {
-        static std::once_flag once;
-        static hipError_t attr_err = hipSuccess;
-        std::call_once(once, [] {
-            attr_err = hipFuncSetAttribute((const void*)k_vq_lookup, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024);
-        });
-        ES_REQUIRE(attr_err == hipSuccess, "es_vq_lookup: hipFuncSetAttribute failed: %s", hipGetErrorString(attr_err));
-    }
+    static const LdsLimits lim{{(const void*)k_vq_lookup, 160 * 1024 - 1024}};
+    ES_REQUIRE(lim.err == hipSuccess, "es_vq_lookup: hipFuncSetAttribute failed: %s", hipGetErrorString(lim.err));
     const long M = (long)a->O * a->V;
     hipLaunchKernelGGL(k_vq_lookup, dim3((unsigned)((M + 255) / 256)), dim3(256), (size_t)a->n_embed * 16, (hipStream_t)stream, *a);
     ES_CHECK_HIP(hipGetLastError());
