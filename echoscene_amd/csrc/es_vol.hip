@@ -2844,6 +2844,13 @@ enum class ConvKernel {
     small_n, small_n_tiled, n16, kw_4_1, kw_2_2, ws_256_8_4_3, ws_64_4_4_3, ws_64_4_4_6, ws_128_4_4_3, ws_128_4_8_3, ws_128_4_8_5, ws3,
     linear_ws, linear_deep, lean_256, lean_128, lean_64
 };
+// the enumerators' spelling, in their order (es_conv_kernel_of): a kernel added to the enum is added here
+static const char* const kConvKernelName[] = {
+    "none",
+    "small_n", "small_n_tiled", "n16", "kw_4_1", "kw_2_2", "ws_256_8_4_3", "ws_64_4_4_3", "ws_64_4_4_6", "ws_128_4_4_3", "ws_128_4_8_3", "ws_128_4_8_5", "ws3",
+    "linear_ws", "linear_deep", "lean_256", "lean_128", "lean_64"
+};
+static_assert(sizeof(kConvKernelName) / sizeof(kConvKernelName[0]) == (size_t)ConvKernel::lean_64 + 1, "kConvKernelName: one name per ConvKernel value");
 enum class ConvReduce { none, plain, gn_part };      // k_conv_splitk_reduce / k_conv_splitk_reduce_gn behind a launch split over workgroups
 struct ConvRoute {
     ConvGeom g;
@@ -2923,6 +2930,7 @@ static int conv_route(const es_conv_args* a, ConvRoute* r) {
             ConvRoute rc;
             if (int err = conv_route(&c, &rc)) return err;
             r->omax = omax;
+            r->S = rc.S;                                       // (es_conv_kernel_of: the split of a full chunk)
             r->slabs = (int)((rc.slabs * omax + a->O - 1) / a->O);
             r->stats_pass = a->gn_stats_out != nullptr;        // (the planes are laid out for the whole tensor: one pass behind the chunks)
             return 0;
@@ -3344,6 +3352,17 @@ extern "C" int es_conv_emits_gn_part(const es_conv_args* a) {
 extern "C" int es_conv_split_of(const es_conv_args* a) {
     ConvRoute r;
     return conv_route(a, &r) == 0 ? r.slabs : -1;
+}
+
+// The name of the kernel es_conv_mfma_f16(args) would launch (the ConvKernel enumerator's spelling; "chunked" for a launch over the
+// 2 GiB descriptor limit, whose chunks are routed one by one; "none" for forcing options that name a tile that is not built),
+// written into name_out (cap bytes, always terminated); returns the split of K over workgroups (ConvRoute::S, >= 1; a chunked
+// launch: of a full chunk), -1 on invalid arguments.  Host-only: tests assert with it that the kernel they mean is the one that ran.
+extern "C" int es_conv_kernel_of(const es_conv_args* a, char* name_out, int cap) {
+    ConvRoute r;
+    if (conv_route(a, &r) != 0) return -1;
+    if (name_out && cap > 0) snprintf(name_out, (size_t)cap, "%s", r.omax ? "chunked" : kConvKernelName[(int)r.kernel]);
+    return r.S > 1 ? r.S : 1;
 }
 
 extern "C" int es_groupnorm_vol(const es_gn_args* a, es_stream stream) {

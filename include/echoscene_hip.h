@@ -316,6 +316,11 @@ int es_conv_emits_gn_part(const es_conv_args* args);
  * split, or K split inside the workgroup); -1 on invalid arguments.  With splitk = -1 the workspace must hold that many slabs (the
  * bounds stated at `splitk` are the maximum).  Launches nothing. */
 int es_conv_split_of(const es_conv_args* args);
+/* host-only: writes the name of the kernel es_conv_mfma_f16(args) would launch ("lean_64", "ws_128_4_8_5", "kw_4_1", "ws3",
+ * "linear_ws", ...; "chunked" for a launch over the 2 GiB descriptor limit, "none" for forcing options that name a tile that is not
+ * built) into name_out (cap bytes, always terminated) and returns the split of K over workgroups (>= 1; a chunked launch: of a full
+ * chunk); -1 on invalid arguments.  For tests and tools: the answer is no part of the numerics contract.  Launches nothing. */
+int es_conv_kernel_of(const es_conv_args* args, char* name_out, int cap);
 /* Split-operand image of an fp32 activation [M, C] (C % 4 == 0): out f16 [M, 3 C] = [hi | lo | hi], hi = f16(x), lo = f16(x - hi).
  * Against a weight image packed from [w_hi | w_hi | w_lo] (Cin = 3 C) es_conv_mfma_f16 accumulates hi w_hi + lo w_hi + hi w_lo in
  * fp32: the reference's fp32 arithmetic to ~2^-21 per product on the f16 matrix pipe (ShapeDenoiser(precision='fp32x')). */

@@ -951,6 +951,8 @@ def test_splitk_reduction_leaves_the_next_groupnorm_partials(dev, monkeypatch, O
                                  # round 6: the few-objects kernels forced for EVERY eligible launch -- producer/consumer tiles of 64 and
                                  # 128 rows, and K split inside the workgroup (4 streams x 112 columns, 2 streams x 224 columns)
                                  {'ES_TEST_VOL_OPTIONS': 'conv_st_bm=64'}, {'ES_TEST_VOL_OPTIONS': 'conv_st_bm=128,conv_st_np=8'},
+                                 # ... and their deeper rings (6 slots of 64 rows, 5 slots of 128 rows with 8 producer waves)
+                                 {'ES_TEST_VOL_OPTIONS': 'conv_st_bm=64,conv_st_ns=6'}, {'ES_TEST_VOL_OPTIONS': 'conv_st_bm=128,conv_st_np=8,conv_st_ns=5'},
                                  {'ES_TEST_VOL_OPTIONS': 'conv_kw_ks=4'}, {'ES_TEST_VOL_OPTIONS': 'conv_kw_ks=2'},
                                  # k_conv_ws3 (A tile of a (chunk, kd, kh) group staged once, kw = -1 / +1 operands shifted in registers) for every
                                  # 3x3x3 SAME conv, small ones included (conv_force256), W = 4 / 8 / 16
@@ -969,9 +971,16 @@ def test_conv_alternate_kernels(env):
     e = dict(os.environ)
     e.update(env)
     here = os.path.dirname(os.path.abspath(__file__))
-    sel = 'test_conv_mfma or test_conv_fused_skip or unet3d_full_eps or vqvae or test_conv_ws_at'
+    sel = 'test_conv_mfma or test_conv_fused_skip or unet3d_full_eps or test_conv_ws_at'
     sel += ' or test_conv_down_dhw or rowgroup_stats'
-    r = subprocess.run([sys.executable, '-m', 'pytest', os.path.join(here, 'test_hip_vol.py'), '-m', 'gpu', '-q', '-x', '-k', sel],
+    # the VQ-VAE's convs (UP_DHW in the decoder, DOWN_DHW_P01 in the encoder, the N = 1 output conv) live in two other files
+    sel += ' or (test_vqvae_decode_vs_reference_golden and tiny) or (test_vqvae_encode_vs_reference_golden and tiny) or test_conv_down_p01_vs_torch'
+    files = [os.path.join(here, f) for f in ('test_hip_vol.py', 'test_hip_scene.py', 'test_hip_keep.py')]
+    if env == {'ES_CONV_A3': '0'}:
+        # (read once per process, so only here: the SAME cases of the kernel x mode matrix with k_conv_ws3's launches on k_conv_ws)
+        files.append(os.path.join(here, 'test_hip_conv_matrix.py'))
+        sel += ' or (test_conv_matrix and same)'
+    r = subprocess.run([sys.executable, '-m', 'pytest'] + files + ['-m', 'gpu', '-q', '-x', '-k', sel],
                        env=e, cwd=os.path.dirname(here), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
