@@ -2,6 +2,11 @@
 //   * k_ddim_blend -- the masked-DDIM blend of DDIMSampler.ddim_sampling (samplers/ddim.py:160-163) with q_sample
 //     (echo2shape.py:254-258), planned in front of every step's denoiser;
 //   * k_conv_c1    -- conv_in of the VQ-VAE encoder (Encoder3D, vqvae_modules.py:205-209): one input channel, 3x3x3, padding 1.
+// Box-preserving sampling (keep given boxes while the others are placed around them):
+//   * k_ddpm_update_keep -- the ancestral layout update (p_sample_sg, diffusion_ddpm.py:296-309) that also leaves the kept nodes' rows
+//     at the NEXT iteration's q_sample (GaussianDiffusion.q_sample, diffusion_ddpm.py:191-201): the masked loop without a launch of
+//     its own in the latency-bound layout step;
+//   * k_box_prescale     -- scale_box_params + preprocess_angle2sincos (helpers/util.py:516-540), the inverse of es_box_postprocess.
 #include "es_common.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -118,6 +123,105 @@ extern "C" int es_conv_c1_f32(const es_conv_c1_args* a, es_stream stream) {
         case 128: hipLaunchKernelGGL(k_conv_c1<32>, grid, blk, 0, st, *a); break;
         default: ES_REQUIRE(false, "es_conv_c1_f32: N=%d output channels (16, 32, 64 or 128)", a->N);
     }
+    ES_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_ddpm_update_keep: es_ddpm_update's arithmetic on the rows whose mask is 0 (the same expressions in the same order as k_ddpm_update,
+// es_rows.hip: the same bits), and on the rows whose mask is 1 the state the denoiser of the NEXT iteration has to see:
+//     st + 1 <  n_tab:  x[i] = tab[2 (st+1)] * x0[i] + tab[2 (st+1) + 1] * keep_noise[st+1][i]      (two products, one sum, uncontracted)
+//     st + 1 == n_tab:  x[i] = x0[i]                                                                (the loop's result: the caller's bits)
+// A kept element reads neither eps nor the step's noise draw, and is never clipped; row st + 1 of tab / keep_noise is only touched
+// when it exists.  ONE_BLOCK as k_ddpm_update: the whole state in one workgroup, which advances the step counter itself.
+// ---------------------------------------------------------------------------------------------
+template <bool ONE_BLOCK>
+__global__ void k_ddpm_update_keep(const es_ddpm_keep_args a) {
+#pragma clang fp contract(off)
+    const int st = *a.step;
+    const float* c = a.coef + (long)st * a.coef_stride;
+    const bool last = st + 1 >= a.n_tab;
+    float ka = 0.0f, kb = 0.0f;
+    if (!last) { ka = a.tab[2 * (st + 1)]; kb = a.tab[2 * (st + 1) + 1]; }
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += ONE_BLOCK ? (int)blockDim.x : a.n) {
+        if (a.mask[i / a.row] != 0.0f) {
+            float v = a.x0[i];
+            if (!last) {
+                const float p = ka * v, q = kb * a.keep_noise[(long)(st + 1) * a.keep_noise_stride + i];
+                v = p + q;
+            }
+            a.x[i] = v;
+            continue;
+        }
+        const float x = a.x[i];
+        const int ns = a.eps_nslab > 1 ? a.eps_nslab : 1;
+        float e = a.eps[i];
+        for (int j = 1; j < ns; ++j) e += a.eps[i + (long)j * a.eps_slab_stride];
+        const float nz = a.noise[(long)st * a.noise_stride + i];
+        float x0 = c[0] * x - c[1] * e;
+        if (a.clip_x0) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);
+        const float mean = c[2] * x0 + c[3] * x;
+        a.x[i] = mean + c[4] * nz;
+    }
+    if (ONE_BLOCK && a.inc_step) {
+        __syncthreads();
+        if (threadIdx.x == 0) *a.step = st + 1;
+    }
+}
+
+__global__ void k_keep_step_inc(int32_t* step) { *step += 1; }
+
+extern "C" int es_ddpm_update_keep(const es_ddpm_keep_args* a, es_stream stream) {
+    ES_REQUIRE(a && a->x && a->eps && a->noise && a->coef && a->step && a->x0 && a->mask && a->keep_noise && a->tab,
+               "es_ddpm_update_keep: NULL argument");
+    ES_REQUIRE(a->n > 0 && a->row > 0 && a->n % a->row == 0 && a->n_tab > 0 && a->coef_stride >= 5 && (long)a->keep_noise_stride >= (long)a->n &&
+               (long)a->noise_stride >= (long)a->n,
+               "es_ddpm_update_keep: n=%d row=%d n_tab=%d coef_stride=%d noise_stride=%d keep_noise_stride=%d (n a multiple of row, strides >= n)",
+               a->n, a->row, a->n_tab, a->coef_stride, a->noise_stride, a->keep_noise_stride);
+    if (a->n <= 4096) {
+        hipLaunchKernelGGL(k_ddpm_update_keep<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, *a);
+    } else {
+        hipLaunchKernelGGL(k_ddpm_update_keep<false>, dim3((a->n + 255) / 256), dim3(256), 0, (hipStream_t)stream, *a);
+        if (a->inc_step) hipLaunchKernelGGL(k_keep_step_inc, dim3(1), dim3(1), 0, (hipStream_t)stream, a->step);
+    }
+    ES_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_box_prescale: metric boxes -> the normalised rows of the layout state.  Column c of ncol (6: sizes | translations, 7: + a metric
+// angle) becomes 2 (v - lo) / (hi - lo) - 1 with the float64 statistics of the dataset (scale_box_params, helpers/util.py:516-532, angle
+// flag :528-530), and an angle becomes (sin, cos) (preprocess_angle2sincos, :534-540).  The reference computes on float64 statistics:
+// everything is evaluated in double here and rounded to fp32 once -- 14 numbers per box.
+// ---------------------------------------------------------------------------------------------
+__global__ void k_box_prescale(const float* boxes, int ld, int ncol, const float* angles, const double* stats, float* out, int out_ld,
+                               float* sincos_out, int O) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= O) return;
+    if (boxes && out) {
+        for (int c = 0; c < ncol; ++c) {
+            const double lo = stats[c < 3 ? c : c < 6 ? 3 + c : 12], hi = stats[c < 3 ? 3 + c : c < 6 ? 6 + c : 13];
+            double v = ((double)boxes[(long)i * ld + c] - lo) / (hi - lo);
+            v = 2.0 * v - 1.0;
+            out[(long)i * out_ld + c] = (float)v;
+        }
+    }
+    if (angles && sincos_out) {
+        const double t = (double)angles[i];
+        sincos_out[2 * i] = (float)sin(t);
+        sincos_out[2 * i + 1] = (float)cos(t);
+    }
+}
+
+extern "C" int es_box_prescale(const float* boxes, int ld, int ncol, const float* angles, const double* stats, float* out, int out_ld,
+                               float* sincos_out, int O, es_stream stream) {
+    ES_REQUIRE(O > 0 && ((boxes && out) || (angles && sincos_out)), "es_box_prescale: nothing to do (O=%d)", O);
+    ES_REQUIRE(!boxes == !out && !angles == !sincos_out, "es_box_prescale: boxes / out and angles / sincos_out go together");
+    ES_REQUIRE(!boxes || (stats && (ncol == 6 || ncol == 7) && ld >= ncol && out_ld >= ncol),
+               "es_box_prescale: bad args (ncol=%d, ld=%d, out_ld=%d)", ncol, ld, out_ld);
+    hipLaunchKernelGGL(k_box_prescale, dim3((O + 63) / 64), dim3(64), 0, (hipStream_t)stream, boxes, ld, ncol, angles, stats, out, out_ld,
+                       sincos_out, O);
     ES_CHECK_HIP(hipGetLastError());
     return 0;
 }

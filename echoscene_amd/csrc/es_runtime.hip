@@ -74,6 +74,7 @@ static int dispatch(const es_op& op, hipStream_t s) {
         case ES_OP_ROWSEL: return es_row_select(&op.u.rowsel, s);
         case ES_OP_DDIM_BLEND: return es_ddim_blend(&op.u.blend, s);
         case ES_OP_CONV_C1: return es_conv_c1_f32(&op.u.conv_c1, s);
+        case ES_OP_DDPM_KEEP: return es_ddpm_update_keep(&op.u.keep, s);
         default: es_set_error("plan: unknown op kind %d", op.kind); return 3;
     }
 }
@@ -288,6 +289,10 @@ extern "C" int es_op_pointer_offsets(int kind, size_t* out, int cap) {
         case ES_OP_CONV_C1:
             v = {ES_PTR(conv_c1.x), ES_PTR(conv_c1.w), ES_PTR(conv_c1.bias), ES_PTR(conv_c1.out_f32), ES_PTR(conv_c1.out_f16)};
             break;
+        case ES_OP_DDPM_KEEP:
+            v = {ES_PTR(keep.x), ES_PTR(keep.eps), ES_PTR(keep.noise), ES_PTR(keep.coef), ES_PTR(keep.step), ES_PTR(keep.x0), ES_PTR(keep.mask),
+                 ES_PTR(keep.keep_noise), ES_PTR(keep.tab)};
+            break;
         case ES_OP_FORK: case ES_OP_JOIN: break;
         default: return -1;
     }
@@ -493,6 +498,11 @@ static es_model* model_load_impl(const char* path, FILE* fp, es_model* m) {
             for (const es_op& op : ops)
                 if ((op.kind == ES_OP_DDPM || op.kind == ES_OP_DDIM) && op.u.update.coef_stride > 0)
                     m->schedule_len = (long)(r.bytes / ((size_t)op.u.update.coef_stride * 4));
+                else if (op.kind == ES_OP_DDPM_KEEP && op.u.keep.coef_stride > 0) {
+                    // the masked loop reads tab / keep_noise by iteration too: the shorter of the two tables bounds the run
+                    const long by_coef = (long)(r.bytes / ((size_t)op.u.keep.coef_stride * 4));
+                    m->schedule_len = by_coef < op.u.keep.n_tab ? by_coef : (long)op.u.keep.n_tab;
+                }
     m->plan = es_plan_create(ops.data(), (int)ops.size());
     return m->plan ? m : nullptr;
 }
@@ -547,6 +557,51 @@ extern "C" int es_layout_sample(es_model* m, const float* noise, int noise_rows,
     hipStream_t s = (hipStream_t)stream;
     ES_CHECK_HIP(hipMemcpyAsync(nz, noise, (size_t)noise_rows * xb, hipMemcpyDeviceToDevice, s));
     ES_CHECK_HIP(hipMemcpyAsync(x, noise, xb, hipMemcpyDeviceToDevice, s));               // x_T = row 0
+    if (int rc = es_model_run(m, 0, n_steps, stream)) return rc;
+    ES_CHECK_HIP(hipMemcpyAsync(x_out, x, xb, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+extern "C" int es_layout_sample_keep(es_model* m, const float* noise, int noise_rows, int n_steps, const float* x0, const float* mask,
+                                     const float* keep_noise, float* x_out, es_stream stream) {
+    ES_REQUIRE(m && m->plan && noise && x0 && mask && keep_noise && x_out && n_steps >= 0 && noise_rows >= n_steps + 1,
+               "es_layout_sample_keep: bad args (noise rows %d, steps %d)", noise_rows, n_steps);
+    const es_ddpm_keep_args* k = nullptr;
+    for (const es_op& op : m->plan->ops) if (op.kind == ES_OP_DDPM_KEEP) k = &op.u.keep;
+    ES_REQUIRE(k, "es_layout_sample_keep: the model was not saved with keep=True (no masked update op)");
+    ES_REQUIRE(n_steps <= k->n_tab, "es_layout_sample_keep: %d steps exceed the model's schedule (%d steps)", n_steps, k->n_tab);
+    void *x = nullptr, *nz = nullptr, *rx0 = nullptr, *rmask = nullptr, *rkn = nullptr, *rtab = nullptr, *step = nullptr;
+    size_t xb = 0, nb = 0, x0b = 0, mb = 0, knb = 0, tb = 0;
+    if (int rc = es_model_region(m, "x", &x, &xb)) return rc;
+    if (int rc = es_model_region(m, "noise", &nz, &nb)) return rc;
+    if (int rc = es_model_region(m, "x0", &rx0, &x0b)) return rc;
+    if (int rc = es_model_region(m, "mask", &rmask, &mb)) return rc;
+    if (int rc = es_model_region(m, "knoise", &rkn, &knb)) return rc;
+    if (int rc = es_model_region(m, "ktab", &rtab, &tb)) return rc;
+    if (int rc = es_model_region(m, "step", &step, nullptr)) return rc;
+    ES_REQUIRE(xb > 0 && x0b == xb && mb > 0 && xb % mb == 0 && (size_t)k->n * 4 == xb && (size_t)k->row * mb == xb,
+               "es_layout_sample_keep: regions x (%zu B), x0 (%zu B), mask (%zu B) do not fit the update op (n=%d, row=%d)", xb, x0b, mb, k->n, k->row);
+    ES_REQUIRE((size_t)noise_rows * xb <= nb, "es_layout_sample_keep: %d noise rows exceed the model's schedule (%zu rows)", noise_rows, nb / xb);
+    ES_REQUIRE(knb >= (size_t)k->n_tab * xb && tb >= (size_t)k->n_tab * 8, "es_layout_sample_keep: knoise / ktab regions shorter than the schedule");
+    hipStream_t s = (hipStream_t)stream;
+    ES_CHECK_HIP(hipMemcpyAsync(nz, noise, (size_t)noise_rows * xb, hipMemcpyDeviceToDevice, s));
+    ES_CHECK_HIP(hipMemcpyAsync(x, noise, xb, hipMemcpyDeviceToDevice, s));               // x_T = row 0
+    ES_CHECK_HIP(hipMemcpyAsync(rx0, x0, xb, hipMemcpyDeviceToDevice, s));
+    ES_CHECK_HIP(hipMemcpyAsync(rmask, mask, mb, hipMemcpyDeviceToDevice, s));
+    // iteration i's update reads row i + 1 while it exists: a run stopped early needs one row more than it has iterations
+    const int kn_rows = n_steps < k->n_tab ? n_steps + 1 : k->n_tab;
+    if (n_steps > 0) ES_CHECK_HIP(hipMemcpyAsync(rkn, keep_noise, (size_t)kn_rows * xb, hipMemcpyDeviceToDevice, s));
+    if (n_steps == 0) {                       // nothing runs: x_T as given (no iteration whose denoiser would read primed rows)
+        ES_CHECK_HIP(hipMemcpyAsync(x_out, x, xb, hipMemcpyDeviceToDevice, s));
+        return 0;
+    }
+    // prime the kept rows of x_T: q_sample(x0, t(0), keep_noise[0]) -- es_ddim_blend at n = row, with the step counter at 0
+    ES_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)step, 0, 1, s));
+    es_blend_args b{};
+    b.x = (float*)x; b.x0 = (const float*)rx0; b.mask = (const float*)rmask; b.noise = (const float*)rkn;
+    b.noise_stride = k->keep_noise_stride; b.tab = (const float*)rtab; b.step = (const int32_t*)step;
+    b.O = k->n / k->row; b.n = k->row;
+    if (int rc = es_ddim_blend(&b, stream)) return rc;
     if (int rc = es_model_run(m, 0, n_steps, stream)) return rc;
     ES_CHECK_HIP(hipMemcpyAsync(x_out, x, xb, hipMemcpyDeviceToDevice, s));
     return 0;

@@ -25,6 +25,7 @@ OP_VQ = 12
 OP_FORK, OP_JOIN, OP_ROWSEL = 13, 14, 15
 OP_CONV_F32, OP_ATTN_F32 = 16, 17          # fp32-operand validation route (csrc/es_vol32.hip)
 OP_DDIM_BLEND, OP_CONV_C1 = 18, 19         # masked-DDIM blend / the VQ-VAE encoder's one-channel conv_in (csrc/es_keep.hip)
+OP_DDPM_KEEP = 21                          # the layout update that also carries the kept rows (csrc/es_keep.hip); 20 stays unassigned
 
 
 class Seg(C.Structure):
@@ -114,6 +115,15 @@ class BlendArgs(C.Structure):
                 ('tab', C.c_void_p), ('step', C.c_void_p), ('O', C.c_int32), ('n', C.c_int32)]
 
 
+class DdpmKeepArgs(C.Structure):
+    _fields_ = [('x', C.c_void_p), ('eps', C.c_void_p), ('eps_nslab', C.c_int32), ('eps_slab_stride', C.c_int32),
+                ('noise', C.c_void_p), ('noise_stride', C.c_int32),
+                ('coef', C.c_void_p), ('coef_stride', C.c_int32), ('step', C.c_void_p), ('n', C.c_int32),
+                ('inc_step', C.c_int32), ('clip_x0', C.c_int32),
+                ('x0', C.c_void_p), ('mask', C.c_void_p), ('keep_noise', C.c_void_p), ('keep_noise_stride', C.c_int32),
+                ('tab', C.c_void_p), ('n_tab', C.c_int32), ('row', C.c_int32)]
+
+
 class ConvC1Args(C.Structure):
     _fields_ = [('x', C.c_void_p), ('w', C.c_void_p), ('bias', C.c_void_p), ('out_f32', C.c_void_p), ('out_f16', C.c_void_p),
                 ('O', C.c_int32), ('D', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('N', C.c_int32)]
@@ -122,7 +132,8 @@ class ConvC1Args(C.Structure):
 class _OpU(C.Union):
     _fields_ = [('linear', LinearArgs), ('update', UpdateArgs), ('copy', CopyArgs), ('conv', ConvArgs),
                 ('gn', GNArgs), ('ln', LNArgs), ('attn', AttnArgs), ('geglu', GegluArgs), ('tocl', ToClArgs),
-                ('stem', StemArgs), ('vq', VQArgs), ('rowsel', RowSelArgs), ('blend', BlendArgs), ('conv_c1', ConvC1Args)]
+                ('stem', StemArgs), ('vq', VQArgs), ('rowsel', RowSelArgs), ('blend', BlendArgs), ('conv_c1', ConvC1Args),
+                ('keep', DdpmKeepArgs)]
 
 
 class Op(C.Structure):
@@ -162,6 +173,9 @@ EXPORTS = {
     'es_ddim_update': (C.c_int, [C.POINTER(UpdateArgs), C.c_void_p]),
     'es_ddim_blend': (C.c_int, [C.POINTER(BlendArgs), C.c_void_p]),
     'es_conv_c1_f32': (C.c_int, [C.POINTER(ConvC1Args), C.c_void_p]),
+    'es_ddpm_update_keep': (C.c_int, [C.POINTER(DdpmKeepArgs), C.c_void_p]),
+    'es_box_prescale': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                  C.c_void_p]),
     'es_box_postprocess': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float,
                                      C.c_void_p]),
     'es_box_descale': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -211,6 +225,8 @@ EXPORTS = {
     'es_model_num_ops': (C.c_int, [C.c_void_p]),
     'es_model_run': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     'es_layout_sample': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'es_layout_sample_keep': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
     'es_shape_sample': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     'es_vq_decode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }

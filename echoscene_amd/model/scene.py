@@ -87,12 +87,13 @@ class EchoToLayout(nn.Module):
 
     @torch.no_grad()
     def generate_layout_sg(self, box_dim, text=None, ret_traj=False, ddim=False, clip_denoised=False,
-                           batch_seeds=None, noise=None):
+                           batch_seeds=None, noise=None, x0=None, mask=None, keep_noise=None):
         """echo2layout.py:112-126.  ``noise`` (optional, f32[T+1,O,box_dim]) makes the run reproducible.
         ``clip_denoised`` reaches the loop (gen_samples_sg, echo2layout.py:108; diffusion_ddpm.py:243-244).  ``ret_traj``, ``ddim``,
         ``text`` and ``batch_seeds`` are accepted and -- exactly as in the reference, whose ``sample`` (echo2layout.py:102-110)
-        passes none of them on -- have no effect."""
-        samples = self._denoiser().sample(self.uc_rel, self.preds, noise=noise, clip_denoised=bool(clip_denoised))
+        passes none of them on -- have no effect.  ``x0`` / ``mask`` / ``keep_noise``: the masked loop (LayoutDenoiser.sample)."""
+        samples = self._denoiser().sample(self.uc_rel, self.preds, noise=noise, clip_denoised=bool(clip_denoised),
+                                          x0=x0, mask=mask, keep_noise=keep_noise)
         s, t = self.size_dim, self.translation_dim
         return {'sizes': samples[:, 0:s].contiguous(),
                 'translations': samples[:, s:s + t].contiguous(),
@@ -352,11 +353,36 @@ class _SceneModel(nn.Module):
         torch.cuda.synchronize()
         return dec_oe, latent, latent_m.t
 
-    def _layout(self, triples, obj_embed_, relation_cond, noise=None):
+    def _box_keep(self, keep_box_nodes, keep_boxes, keep_box_noise, n_objects, device):
+        """``keep_box_nodes`` / ``keep_boxes`` / ``keep_box_noise`` of the sampling calls -> keyword arguments of the masked layout loop
+        (LayoutDenoiser.sample): x0 [O, 8] with the kept nodes' rows, mask [O].  ``keep_boxes`` f32 [K, 8] = sizes | translations |
+        angles in the model's normalised space -- ``torch.cat`` of the rows these calls return -- one row per entry of
+        ``keep_box_nodes`` (indices into the decoder-side node list; duplicates and out-of-range entries as samplers.keep_selection)."""
+        if (keep_box_nodes is None) != (keep_boxes is None):
+            raise ValueError('keep_box_nodes and keep_boxes go together')
+        if keep_box_nodes is None:
+            if keep_box_noise is not None:
+                raise ValueError('keep_box_noise without keep_box_nodes / keep_boxes')
+            return {}
+        from ..samplers import keep_selection
+        nodes = [int(t) for t in (keep_box_nodes.tolist() if torch.is_tensor(keep_box_nodes) else keep_box_nodes)]
+        boxes = torch.as_tensor(keep_boxes)
+        D = self.LayoutDiff.bbox_dim
+        if boxes.dim() != 2 or tuple(boxes.shape) != (len(nodes), D):
+            raise ValueError('keep_boxes must be [len(keep_box_nodes), %d] (sizes | translations | angles, normalised: one row per '
+                             'entry of keep_box_nodes); got %s for %d nodes' % (D, tuple(boxes.shape), len(nodes)))
+        mask, rows, src = keep_selection(nodes, n_objects)
+        x0 = torch.zeros(n_objects, D, device=device)
+        if rows:
+            x0[rows] = boxes[src].to(device).float()
+        return dict(x0=x0, mask=mask.to(device), keep_noise=keep_box_noise)
+
+    def _layout(self, triples, obj_embed_, relation_cond, noise=None, keep_box_nodes=None, keep_boxes=None, keep_box_noise=None):
+        kw = self._box_keep(keep_box_nodes, keep_boxes, keep_box_noise, obj_embed_.shape[0], obj_embed_.device)
         self.LayoutDiff.set_input({'preds': triples, 'box': None, 'uc_b': obj_embed_, 'c_b': relation_cond,
                                    'obj_id_to_scene': None})
         return self.LayoutDiff.generate_layout_sg(box_dim=self.diff_cfg.layout_branch.denoiser_kwargs.in_channels,
-                                                  noise=noise)
+                                                  noise=noise, **kw)
 
 
 class Sg2ScDiffModel(_SceneModel):
@@ -407,20 +433,26 @@ class Sg2ScDiffModel(_SceneModel):
                                         noise=shape_noise)
 
     def _layout_and_shapes(self, gen_shape, dec_objs, dec_triples, obj_embed_, latent, layout_noise, shape_noise,
-                           keep_nodes=None, keep_sdfs=None, keep_noise=None):
+                           keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None, keep_boxes=None,
+                           keep_box_noise=None):
         """The two loops only share the setup (the reference runs them back to back, EchoScene.py:402-419).  Here they are
         ONE replayed hipGraph: each replay is a DDIM shape step with ten ancestral layout steps on a parallel branch
         (samplers.sample_layout_and_shape), then the VQ-VAE decode.
 
         ``keep_nodes`` / ``keep_sdfs`` (shape-preserving sampling): the listed nodes keep the SDFs the caller hands in -- their encoded
         latents follow the forward-noised trajectory of the masked DDIM loop (and take part in every step's message passing) while
-        the other nodes are generated; the returned rows ``keep_nodes`` are the caller's SDFs themselves."""
+        the other nodes are generated; the returned rows ``keep_nodes`` are the caller's SDFs themselves.
+
+        ``keep_box_nodes`` / ``keep_boxes`` (box-preserving sampling, independent of the above; with or without gen_shape): the listed
+        nodes keep the normalised boxes the caller hands in (_box_keep) -- the masked ancestral layout loop -- and the returned
+        sizes / translations / angles rows of those nodes are the caller's numbers bit for bit."""
         if (keep_nodes is None) != (keep_sdfs is None):
             raise ValueError('keep_nodes and keep_sdfs go together')
         if not gen_shape:
             if keep_nodes is not None:
                 raise ValueError('keep_nodes / keep_sdfs keep SHAPES: they need gen_shape=True')
-            return None, self._layout(dec_triples, obj_embed_, latent, layout_noise)
+            return None, self._layout(dec_triples, obj_embed_, latent, layout_noise, keep_box_nodes, keep_boxes, keep_box_noise)
+        bk = self._box_keep(keep_box_nodes, keep_boxes, keep_box_noise, obj_embed_.shape[0], obj_embed_.device)
         from ..samplers import sample_layout_and_shape
         uc = self._rel_s(obj_embed_)
         c = self._rel_s(latent)
@@ -437,6 +469,8 @@ class Sg2ScDiffModel(_SceneModel):
         if keep_nodes is not None:
             x0, mask, rows, kept = S.keep_inputs(keep_nodes, keep_sdfs, uc.shape[0], sden.device)
             kw = dict(x0=x0, mask=mask, keep_noise=keep_noise)
+        if bk:
+            kw.update(box_x0=bk['x0'], box_mask=bk['mask'], box_keep_noise=bk['keep_noise'])
         x, z = sample_layout_and_shape(L._denoiser(), sden, obj_embed_, dec_triples, uc, c if need_c else None,
                                        layout_noise=layout_noise, shape_noise=shape_noise, **kw)
         s_, t_ = L.size_dim, L.translation_dim
@@ -461,16 +495,18 @@ class Sg2ScDiffModel(_SceneModel):
 
     @torch.no_grad()
     def sample(self, dec_objs, dec_triplets, dec_text_feat, dec_rel_feat, gen_shape=False, layout_noise=None,
-               shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None):
-        """EchoScene.py:388-420.  ``keep_nodes`` / ``keep_sdfs`` (keyword-only): see _layout_and_shapes."""
+               shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None,
+               keep_boxes=None, keep_box_noise=None):
+        """EchoScene.py:388-420.  ``keep_nodes`` / ``keep_sdfs`` and ``keep_box_nodes`` / ``keep_boxes`` (keyword-only): see
+        _layout_and_shapes."""
         oe, _, latent_m = self._setup(dec_objs, dec_triplets, dec_text_feat, dec_rel_feat,
                                       dec_objs, dec_triplets, dec_text_feat, dec_rel_feat)
         sdf, boxes = self._layout_and_shapes(gen_shape, dec_objs, dec_triplets, oe, latent_m, layout_noise, shape_noise,
-                                             keep_nodes, keep_sdfs, keep_noise)
+                                             keep_nodes, keep_sdfs, keep_noise, keep_box_nodes, keep_boxes, keep_box_noise)
         return {'shapes': sdf}, boxes
 
     def _edited(self, enc, dec, touched, added, gen_shape, layout_noise, shape_noise, keep_nodes=None, keep_sdfs=None,
-                keep_noise=None):
+                keep_noise=None, keep_box_nodes=None, keep_boxes=None, keep_box_noise=None):
         oe, latent, latent_m = self._setup(*enc, *dec, change_rows=touched, added_rows=added)
         if not self.replace_all_latent:
             latent = latent.clone()
@@ -480,7 +516,7 @@ class Sg2ScDiffModel(_SceneModel):
         else:
             latent = latent_m
         sdf, boxes = self._layout_and_shapes(gen_shape, dec[0], dec[1], oe, latent, layout_noise, shape_noise,
-                                             keep_nodes, keep_sdfs, keep_noise)
+                                             keep_nodes, keep_sdfs, keep_noise, keep_box_nodes, keep_boxes, keep_box_noise)
         keep = torch.ones(len(boxes['translations']), 1, device=oe.device)
         for t in touched:
             if 0 <= int(t) < keep.shape[0]:
@@ -490,16 +526,19 @@ class Sg2ScDiffModel(_SceneModel):
     @torch.no_grad()
     def sample_with_changes(self, enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triplets,
                             dec_text_feat, dec_rel_feat, manipulated_nodes, gen_shape=False, layout_noise=None,
-                            shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None):
+                            shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None,
+               keep_boxes=None, keep_box_noise=None):
         """EchoScene.py:422-472.  ``keep_nodes`` / ``keep_sdfs`` (keyword-only): see _layout_and_shapes."""
         return self._edited((enc_objs, enc_triples, enc_text_feat, enc_rel_feat),
                             (dec_objs, dec_triplets, dec_text_feat, dec_rel_feat),
-                            list(manipulated_nodes), [], gen_shape, layout_noise, shape_noise, keep_nodes, keep_sdfs, keep_noise)
+                            list(manipulated_nodes), [], gen_shape, layout_noise, shape_noise, keep_nodes, keep_sdfs, keep_noise,
+                            keep_box_nodes, keep_boxes, keep_box_noise)
 
     @torch.no_grad()
     def sample_with_additions(self, enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triplets,
                               dec_text_feat, dec_rel_feat, missing_nodes, gen_shape=False, layout_noise=None,
-                              shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None):
+                              shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None,
+               keep_boxes=None, keep_box_noise=None):
         """EchoScene.py:474-532: zero rows inserted at ``missing_nodes[i] + i``; note the reference draws the
         change noise for rows listed in ``missing_nodes`` (:489-494) but splices / masks ``nodes_added``."""
         added = [m + i for i, m in enumerate(missing_nodes)]
@@ -513,7 +552,7 @@ class Sg2ScDiffModel(_SceneModel):
         else:
             latent = latent_m
         sdf, boxes = self._layout_and_shapes(gen_shape, dec_objs, dec_triplets, oe, latent, layout_noise, shape_noise,
-                                             keep_nodes, keep_sdfs, keep_noise)
+                                             keep_nodes, keep_sdfs, keep_noise, keep_box_nodes, keep_boxes, keep_box_noise)
         keep = torch.ones(len(boxes['translations']), 1, device=oe.device)
         for t in added:
             keep[t] = 0
@@ -539,16 +578,19 @@ class Sg2BoxDiffModel(_SceneModel):
 
     # EchoLayout's manipulator uses pred_embeddings_man_dc (EchoLayout.py:154), EchoScene pred_embeddings_ec
     @torch.no_grad()
-    def sampleBoxes(self, dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat, layout_noise=None):
-        """EchoLayout.py:291-307."""
+    def sampleBoxes(self, dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat, layout_noise=None, *,
+                    keep_box_nodes=None, keep_boxes=None, keep_box_noise=None):
+        """EchoLayout.py:291-307.  ``keep_box_nodes`` / ``keep_boxes`` (keyword-only): those nodes keep the given normalised boxes
+        (_SceneModel._box_keep); also on the two editing calls."""
         oe, _, latent_m = self._setup(dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat,
                                       dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat,
                                       manip_pred_table='pred_embeddings_man_dc')
-        return self._layout(dec_triplets, oe, latent_m, layout_noise)
+        return self._layout(dec_triplets, oe, latent_m, layout_noise, keep_box_nodes, keep_boxes, keep_box_noise)
 
     @torch.no_grad()
     def sampleBoxes_with_changes(self, enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triples,
-                                 dec_text_feat, dec_rel_feat, manipulated_nodes, layout_noise=None):
+                                 dec_text_feat, dec_rel_feat, manipulated_nodes, layout_noise=None, *, keep_box_nodes=None,
+                                 keep_boxes=None, keep_box_noise=None):
         touched = list(manipulated_nodes)
         oe, latent, latent_m = self._setup(enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triples,
                                            dec_text_feat, dec_rel_feat, change_rows=touched,
@@ -560,7 +602,7 @@ class Sg2BoxDiffModel(_SceneModel):
                     latent[t] = latent_m[t]
         else:
             latent = latent_m
-        boxes = self._layout(dec_triples, oe, latent, layout_noise)
+        boxes = self._layout(dec_triples, oe, latent, layout_noise, keep_box_nodes, keep_boxes, keep_box_noise)
         # f32 [O,1] tensor on the model's device (EchoLayout.py:342-348); only the _with_additions variant returns a list
         keep = torch.ones(len(boxes['translations']), 1, device=oe.device)
         for t in touched:
@@ -570,7 +612,8 @@ class Sg2BoxDiffModel(_SceneModel):
 
     @torch.no_grad()
     def sampleBoxes_with_additions(self, enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triples,
-                                   dec_text_feat, dec_rel_feat, missing_nodes, layout_noise=None):
+                                   dec_text_feat, dec_rel_feat, missing_nodes, layout_noise=None, *, keep_box_nodes=None,
+                                   keep_boxes=None, keep_box_noise=None):
         added = [m + i for i, m in enumerate(missing_nodes)]
         oe, latent, latent_m = self._setup(enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triples,
                                            dec_text_feat, dec_rel_feat, change_rows=added,   # sic: nodes_added here,
@@ -581,7 +624,7 @@ class Sg2BoxDiffModel(_SceneModel):
                 latent[t] = latent_m[t]
         else:
             latent = latent_m
-        boxes = self._layout(dec_triples, oe, latent, layout_noise)
+        boxes = self._layout(dec_triples, oe, latent, layout_noise, keep_box_nodes, keep_boxes, keep_box_noise)
         keep = [0 if i in added else 1 for i in range(len(boxes['translations']))]
         return keep, boxes
 
@@ -654,15 +697,25 @@ class SGDiff(nn.Module):
         if self.type_ == 'echolayout' and any(kw.get(k) is not None for k in ('keep_nodes', 'keep_sdfs', 'keep_noise')):
             raise ValueError("keep_nodes / keep_sdfs keep SHAPES; an 'echolayout' model has no shape branch")
 
+    @staticmethod
+    def _box_kw(kw):
+        return {k: kw.get(k) for k in ('keep_box_nodes', 'keep_boxes', 'keep_box_noise')}
+
     def sample_box_and_shape(self, dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat, gen_shape=False,
                              **noise):
         """``keep_nodes`` (indices into the decoder-side node list) + ``keep_sdfs`` f32 [K,1,64,64,64] (keyword-only, with
         gen_shape=True): those nodes keep the given truncated SDFs -- rows ``keep_nodes`` of the returned ``shapes`` are the caller's
-        tensors bit for bit -- and the other nodes are generated in their context (masked DDIM).  Also on the two editing calls."""
+        tensors bit for bit -- and the other nodes are generated in their context (masked DDIM).  Also on the two editing calls.
+        ``keep_box_nodes`` + ``keep_boxes`` f32 [K, 8] (keyword-only; 'echoscene' with or without gen_shape, and 'echolayout'): those
+        nodes keep the given boxes -- rows laid out sizes | translations | angles in the model's normalised space, i.e. ``torch.cat`` of
+        the rows this call returns (postprocess.scale_box_params / preprocess_angle2sincos bring metric boxes there) -- while the other
+        nodes are placed in their context (the masked ancestral loop); the returned rows of the kept nodes are the caller's numbers
+        bit for bit.  ``keep_box_noise`` f32 [T, O, 8]: the forward-noising draws (None: drawn on the device).  Independent of
+        ``keep_nodes`` / ``keep_sdfs``; also on the two editing calls."""
         self._no_keep_without_shapes(noise)
         if self.type_ == 'echolayout':
             return self.diff.sampleBoxes(dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat,
-                                         layout_noise=noise.get('layout_noise'))
+                                         layout_noise=noise.get('layout_noise'), **self._box_kw(noise))
         shape_dict, layout_dict = self.diff.sample(dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat,
                                                    gen_shape=gen_shape, **noise)
         return {**shape_dict, **layout_dict}
@@ -674,7 +727,7 @@ class SGDiff(nn.Module):
         if self.type_ == 'echolayout':
             return self.diff.sampleBoxes_with_changes(enc_objs, enc_triples, encoded_enc_text_feat, encoded_enc_rel_feat,
                                                       dec_objs, dec_triples, encoded_dec_text_feat, encoded_dec_rel_feat,
-                                                      manipulated_nodes, layout_noise=noise.get('layout_noise'))
+                                                      manipulated_nodes, layout_noise=noise.get('layout_noise'), **self._box_kw(noise))
         keep, shape_dict, layout_dict = self.diff.sample_with_changes(
             enc_objs, enc_triples, encoded_enc_text_feat, encoded_enc_rel_feat, dec_objs, dec_triples,
             encoded_dec_text_feat, encoded_dec_rel_feat, manipulated_nodes, gen_shape=gen_shape, **noise)
@@ -687,7 +740,7 @@ class SGDiff(nn.Module):
         if self.type_ == 'echolayout':
             keep, layout_dict = self.diff.sampleBoxes_with_additions(
                 enc_objs, enc_triples, encoded_enc_text_feat, encoded_enc_rel_feat, dec_objs, dec_triples,
-                encoded_dec_text_feat, encoded_dec_rel_feat, missing_nodes, layout_noise=noise.get('layout_noise'))
+                encoded_dec_text_feat, encoded_dec_rel_feat, missing_nodes, layout_noise=noise.get('layout_noise'), **self._box_kw(noise))
             return layout_dict                 # sic: the reference drops ``keep`` here (SGDiff.py:113-115)
         keep, shape_dict, layout_dict = self.diff.sample_with_additions(
             enc_objs, enc_triples, encoded_enc_text_feat, encoded_enc_rel_feat, dec_objs, dec_triples,

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import hip
-from .hip import Seg, LinearArgs, UpdateArgs, CopyArgs, RowSelArgs, Op
+from .hip import Seg, LinearArgs, UpdateArgs, DdpmKeepArgs, CopyArgs, RowSelArgs, Op
 
 
 # K-slice choices of the rows planner.  They change where a K sum is cut -- i.e. the fp32 bits of the results -- so they are
@@ -556,6 +556,34 @@ class Builder:
         op.u.update = a
         self.ops.append(op)
 
+    def update_keep(self, x, eps, coef, step, noise, noise_stride, x0, mask, keep_noise, tab, inc_step=True, clip_x0=False):
+        """the ancestral layout update that also carries the kept rows (es_ddpm_update_keep): ``update(OP_DDPM, ...)`` on the rows whose
+        mask is 0, the next iteration's q_sample of ``x0`` (or ``x0`` itself after the last one) on the others.  x, x0 [O, row];
+        mask [O]; keep_noise [T, O * row]; tab [T, 2] (LayoutSchedule.keep_tab)"""
+        a = DdpmKeepArgs()
+        if isinstance(eps, View):
+            assert eps.ld == eps.width and eps.col == 0
+            a.x, a.eps, a.eps_nslab, a.eps_slab_stride = x.data_ptr(), eps.ptr, eps.nslab, eps.slab_stride
+            self.keep.append(eps.t)
+        else:
+            a.x, a.eps = x.data_ptr(), eps.data_ptr()
+        a.noise, a.noise_stride = noise.ptr, noise_stride
+        a.coef, a.coef_stride = coef.data_ptr(), coef.shape[1]
+        a.step = step.data_ptr()
+        a.n = x.numel()
+        a.inc_step = 1 if inc_step else 0
+        a.clip_x0 = 1 if clip_x0 else 0
+        a.x0, a.mask, a.keep_noise = x0.data_ptr(), mask.data_ptr(), keep_noise.data_ptr()
+        a.keep_noise_stride = keep_noise.shape[1]
+        a.tab, a.n_tab = tab.data_ptr(), tab.shape[0]
+        a.row = x.numel() // x.shape[0]
+        assert mask.numel() == x.shape[0] and x0.numel() == x.numel() and keep_noise.shape[0] >= tab.shape[0] and coef.shape[0] >= tab.shape[0]
+        op = Op()
+        op.kind, op.lane = hip.OP_DDPM_KEEP, 0
+        op.u.keep = a
+        self.ops.append(op)
+        self.keep += [x0, mask, keep_noise, tab]
+
     def rowsel(self, table, step, out, rows=1):
         """out[r, :n] = table[*step, :n] for r < rows (out: View; table: 2-D tensor [n_steps, n])"""
         a = RowSelArgs()
@@ -581,6 +609,26 @@ class Builder:
         return Plan(self)
 
 
+def count_launches(ops):
+    """kernel launches of one execution of an op list: the runtime's grouping of rows products marked ``fuse_next`` (es_plan_run: up to
+    three independent products per grid), one launch per other op, + the step increment behind a sampler update"""
+    i, n = 0, 0
+    while i < len(ops):
+        op, k = ops[i], 1
+        if op.kind == hip.OP_LINEAR and op.u.linear.fuse_next:
+            while k < 3 and ops[i + k - 1].u.linear.fuse_next and i + k < len(ops) and ops[i + k].kind == hip.OP_LINEAR \
+                    and ops[i + k].lane == op.lane:
+                k += 1
+        if op.kind not in (hip.OP_FORK, hip.OP_JOIN):
+            n += 1
+        if op.kind in (hip.OP_DDPM, hip.OP_DDIM) and op.u.update.inc_step and not (op.kind == hip.OP_DDPM and op.u.update.n <= 4096):
+            n += 1                           # (the one-workgroup DDPM update advances the step counter itself)
+        if op.kind == hip.OP_DDPM_KEEP and op.u.keep.inc_step and op.u.keep.n > 4096:
+            n += 1                           # (es_ddpm_update_keep: as OP_DDPM)
+        i += k
+    return n
+
+
 class Plan:
     def __init__(self, b):
         self.keep = b.keep
@@ -597,21 +645,8 @@ class Plan:
 
     @property
     def n_launches(self):
-        """kernel launches of one execution: the runtime's grouping of rows products marked ``fuse_next`` (es_plan_run: up to three
-        independent products per grid), one launch per other op, + the step increment behind a sampler update"""
-        ops, i, n = self._arr, 0, 0
-        while i < len(ops):
-            op, k = ops[i], 1
-            if op.kind == hip.OP_LINEAR and op.u.linear.fuse_next:
-                while k < 3 and ops[i + k - 1].u.linear.fuse_next and i + k < len(ops) and ops[i + k].kind == hip.OP_LINEAR \
-                        and ops[i + k].lane == op.lane:
-                    k += 1
-            if op.kind not in (hip.OP_FORK, hip.OP_JOIN):
-                n += 1
-            if op.kind in (hip.OP_DDPM, hip.OP_DDIM) and op.u.update.inc_step and not (op.kind == hip.OP_DDPM and op.u.update.n <= 4096):
-                n += 1                           # (the one-workgroup DDPM update advances the step counter itself)
-            i += k
-        return n
+        """kernel launches of one execution (count_launches)"""
+        return count_launches(self._arr)
 
     def run(self):
         hip.check(hip.lib().es_plan_run(C.c_void_p(self.handle), hip.current_stream()), 'es_plan_run')

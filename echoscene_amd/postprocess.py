@@ -25,6 +25,36 @@ def descale_box_params(normed_box_params, file=None, angle=False, stats=None):
     return x
 
 
+def scale_box_params(box_params, file=None, angle=False, stats=None):
+    """Dataset units -> [-1,1] for sizes (cols 0:3) and translations (cols 3:6) of a float32 CUDA tensor [O, >=6], in place and
+    returned; ``angle=True``: also column 6, a metric angle, from [stats[12], stats[13]] (helpers/util.py:516-532, which handles one box
+    at a time).  The inverse of ``descale_box_params``: a box of a dataset scene or of a de-normalised result becomes a row that
+    ``keep_boxes`` takes.  Evaluated in double on the float64 statistics and rounded once (es_box_prescale)."""
+    assert file is not None or stats is not None
+    ncol = 7 if angle else 6
+    st = np.loadtxt(file) if stats is None else np.asarray(stats, dtype=np.float64)
+    if st.size != 14:
+        raise NotImplementedError('scale_box_params: %d statistics given, 14 needed (helpers/util.py:519-522)' % st.size)
+    x = box_params
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] >= ncol and x.stride(1) == 1):
+        raise ValueError('scale_box_params: expects a float32 CUDA tensor [O, >=%d]' % ncol)
+    std = torch.tensor(st.reshape(-1), dtype=torch.float64, device=x.device)
+    hip.check(hip.lib().es_box_prescale(C.c_void_p(x.data_ptr()), x.stride(0), ncol, None, C.c_void_p(std.data_ptr()),
+                                        C.c_void_p(x.data_ptr()), x.stride(0), None, x.shape[0], hip.current_stream()), 'es_box_prescale')
+    return x
+
+
+def preprocess_angle2sincos(angle):
+    """[O,1] angle in radians -> [O,2] (sin, cos) (helpers/util.py:534-540); the inverse of ``postprocess_sincos2arctan``."""
+    if not (angle.is_cuda and angle.dtype == torch.float32 and angle.dim() == 2 and angle.shape[1] == 1):
+        raise ValueError('preprocess_angle2sincos: expects a float32 CUDA tensor [O, 1]')
+    a = angle.contiguous()
+    out = torch.empty(a.shape[0], 2, dtype=torch.float32, device=a.device)
+    hip.check(hip.lib().es_box_prescale(None, 0, 0, C.c_void_p(a.data_ptr()), None, None, 0, C.c_void_p(out.data_ptr()), a.shape[0],
+                                        hip.current_stream()), 'es_box_prescale')
+    return out
+
+
 def postprocess_sincos2arctan(sincos):
     """[O,2] (sin, cos) -> [O,1] angle in radians."""
     B, N = sincos.shape

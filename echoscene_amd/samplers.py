@@ -62,19 +62,23 @@ class LayoutDenoiser:
         self.T = self.sched.time_num
         self.temb = timestep_embedding_table(self.sched.timesteps, net.model_channels).to(self.device)
         self.coef = self.sched.coef.to(self.device)
+        self.keep_tab = self.sched.keep_tab.to(self.device)      # masked loop: q_sample's factors per iteration (es_ddpm_update_keep)
         # time MLP / emb projections / box_time_emb for every step of the schedule (node-independent)
         self.tables = time_tables(self.w, self.temb, self.w.box_t, self.device)
         self._plans, self._last, self.max_plans = {}, None, 4
 
-    def _plan_for(self, obj_embed, triples, clip=False):
+    def _plan_for(self, obj_embed, triples, clip=False, keep=False):
         """``clip``: clip_denoised=True of p_sample_loop_sg (the predicted x0 clamped to [-1, 1], diffusion_ddpm.py:243-244) -- a
         property of the plan's update op, so it is part of the cache key.
+        ``keep``: the plan of the MASKED loop (keep given boxes) -- the same ops with the LAST one, the update, replaced by the update
+        that also carries the kept rows (es_ddpm_update_keep), and its inputs ``x0`` [O, 8], ``mask`` [O], ``knoise`` [T, O * 8].  A
+        cache entry of its own, as 'clip' is (the two combine): without a mask the plan is, op for op, what it has always been.
         Plans are cached by (node count, triple-row capacity): a NEW scene graph of the same size class only rewrites the
         index arrays and the predicate-embedding rows in place (GraphIndex.update) -- no plan rebuild, no graph re-capture
         (0.3 s per scene in round 1).  Capacity = triple count rounded up to a multiple of 32."""
         O = obj_embed.shape[0]
         cap = _cap(triples.shape[0])
-        key = (O, cap) if not clip else (O, cap, 'clip')
+        key = (O, cap) + (('clip',) if clip else ()) + (('keep',) if keep else ())
         sig = hash(triples.detach().cpu().numpy().tobytes())
         st = self._plans.get(key)
         if st is None:
@@ -88,8 +92,15 @@ class LayoutDenoiser:
             objbuf = emit_unet1d_step(b, self.w, g, x, oe, self.temb, step, None, tables=self.tables)
             eps = b.tags['eps']                                  # View: the output conv's K slices (the update sums the slabs)
             n_eps_ops = len(b.ops)
-            b.update(hip.OP_DDPM, x, eps, self.coef, step, noise=View(noise[1:].reshape(self.T, O * D), ld=O * D),
-                     noise_stride=O * D, inc_step=True, clip_x0=clip)
+            kx0 = kmask = knoise = None
+            if keep:
+                kx0, kmask = b.buf(O, D, zero=True), b.buf(O, zero=True)
+                knoise = b.buf(self.T, O * D, zero=True)
+                b.update_keep(x, eps, self.coef, step, View(noise[1:].reshape(self.T, O * D), ld=O * D), O * D, kx0, kmask, knoise,
+                              self.keep_tab, inc_step=True, clip_x0=clip)
+            else:
+                b.update(hip.OP_DDPM, x, eps, self.coef, step, noise=View(noise[1:].reshape(self.T, O * D), ld=O * D),
+                         noise_stride=O * D, inc_step=True, clip_x0=clip)
             plan = b.finish()
             # eps-only plan (same ops minus the update) for step-level parity tests
             b2 = Builder(self.device)
@@ -97,7 +108,7 @@ class LayoutDenoiser:
             b2.keep = b.keep
             b2.tags = b.tags
             st = dict(plan=plan, eps_plan=b2.finish(), x=x, eps=eps, step=step, noise=noise, objbuf=objbuf,
-                      oe_w=oe.shape[1], g=g, pred=b.pred_rows, sig=sig)
+                      oe_w=oe.shape[1], g=g, pred=b.pred_rows, sig=sig, x0=kx0, mask=kmask, knoise=knoise)
             if len(self._plans) >= self.max_plans:               # a few size classes stay resident
                 self._plans.pop(next(iter(self._plans)))
             self._plans[key] = st
@@ -113,11 +124,16 @@ class LayoutDenoiser:
     def weight_bytes_per_step(self):
         return self._last['plan'].weight_bytes
 
-    def save_model(self, path, obj_embed, triples):
-        """The layout loop of this scene graph as a model file for hosts without Python (es_model_load + es_layout_sample)."""
+    def save_model(self, path, obj_embed, triples, keep=False):
+        """The layout loop of this scene graph as a model file for hosts without Python (es_model_load + es_layout_sample).
+        ``keep=True``: the masked loop (es_layout_sample_keep); the file also names the regions "x0" [O, 8], "mask" [O], "knoise"
+        [T, O * 8] and "ktab" [T, 2]."""
         from .plan import save_model
-        st = self._plan_for(obj_embed, triples)
-        return save_model(st['plan'], path, dict(x=st['x'], noise=st['noise'], step=st['step'], coef=self.coef))
+        st = self._plan_for(obj_embed, triples, keep=keep)
+        regions = dict(x=st['x'], noise=st['noise'], step=st['step'], coef=self.coef)
+        if keep:
+            regions.update(x0=st['x0'], mask=st['mask'], knoise=st['knoise'], ktab=self.keep_tab)
+        return save_model(st['plan'], path, regions)
 
     def eps(self, x, obj_embed, triples, iteration):
         """One UNet1DModel.forward at loop iteration ``iteration`` (t = T-1-iteration)."""
@@ -127,18 +143,66 @@ class LayoutDenoiser:
         torch.cuda.synchronize()
         return st['eps'].value()
 
-    def sample(self, obj_embed, triples, noise=None, n_steps=None, use_graph=True, clip_denoised=False):
+    def _fill_keep(self, st, x0, mask, keep_noise):
+        """inputs of the masked loop into the plan's buffers (validation as ShapeDenoiser._fill_keep)"""
+        O, D = st['x'].shape
+        mask = torch.as_tensor(mask, dtype=torch.float32).reshape(-1)
+        x0 = torch.as_tensor(x0)
+        if mask.numel() != O or tuple(x0.shape) != (O, D):
+            raise ValueError('masked layout loop: x0 must be [O, %d] = %s and mask [O]; got %s and %d entries'
+                             % (D, (O, D), tuple(x0.shape), mask.numel()))
+        if not bool(((mask == 0) | (mask == 1)).all()):
+            raise ValueError('masked layout loop: the mask is per node, 0 (generate) or 1 (keep)')
+        if keep_noise is not None and (keep_noise.dim() < 2 or keep_noise.shape[0] < self.T or keep_noise[0].numel() != O * D):
+            raise ValueError('masked layout loop: keep_noise must be [T, O, %d] with T = %d' % (D, self.T))
+        st['x0'].copy_(x0.to(self.device).float())
+        st['mask'].copy_(mask.to(self.device))
+        if keep_noise is None:
+            st['knoise'].normal_()
+        else:
+            st['knoise'].copy_(keep_noise.to(self.device).float()[:self.T].reshape(self.T, O * D))
+
+    def _prime_keep(self, st):
+        """kept rows of x_T <- q_sample(x0, t of iteration 0, keep_noise[0]): the one launch in front of the masked loop
+        (es_ddim_blend does exactly this arithmetic at n = 8); every later q_sample is written by the step's update launch"""
+        O, D = st['x'].shape
+        a = hip.BlendArgs()
+        a.x, a.x0, a.mask, a.noise = st['x'].data_ptr(), st['x0'].data_ptr(), st['mask'].data_ptr(), st['knoise'].data_ptr()
+        a.noise_stride, a.tab, a.step, a.O, a.n = O * D, self.keep_tab.data_ptr(), st['step'].data_ptr(), O, D
+        st['step'].zero_()
+        import ctypes
+        hip.check(hip.lib().es_ddim_blend(ctypes.byref(a), hip.current_stream()), 'es_ddim_blend')
+
+    def sample(self, obj_embed, triples, noise=None, n_steps=None, use_graph=True, clip_denoised=False, x0=None, mask=None,
+               keep_noise=None):
         """p_sample_loop_sg: returns x_0 [O, 8].  ``noise`` f32[T+1, O, 8] (row 0 = x_T, row 1+i = draw of
         iteration i) makes the run reproducible against the CPU oracle; None draws it on the device.
-        ``clip_denoised``: clamp the predicted x0 to [-1, 1] in every step (diffusion_ddpm.py:243-244; the shipped call passes False)."""
-        st = self._plan_for(obj_embed, triples, clip=bool(clip_denoised))
+        ``clip_denoised``: clamp the predicted x0 to [-1, 1] in every step (diffusion_ddpm.py:243-244; the shipped call passes False).
+
+        Masked loop -- keep given boxes while the others are placed around them: ``mask`` [O] with 1 = keep, 0 = generate, ``x0`` f32
+        [O, 8] the kept nodes' rows in the model's normalised space (rows with mask 0 are not read) and ``keep_noise`` f32 [T, O, 8]
+        the draws of q_sample, row i for iteration i (None: drawn on the device).  Before the denoiser of iteration i (t = T-1-i) the
+        kept rows are ``sqrt_ac[t] * x0 + sqrt(1 - ac)[t] * keep_noise[i]`` (GaussianDiffusion.q_sample, diffusion_ddpm.py:191-201; the
+        reference defines the masked loop for shapes only, samplers/ddim.py:160-163); they take part in the step's message passing
+        like every other node; after the last iteration they are ``x0`` bit for bit.  A run stopped early (``n_steps`` < T) leaves
+        them at the NEXT timestep's forward-noised value.  ``clip_denoised`` never touches kept rows.  ``mask=None``: the loop and
+        its plan are what they are without this feature."""
+        if (mask is None) != (x0 is None):
+            raise ValueError('the masked layout loop needs both x0 and mask')
+        if mask is None and keep_noise is not None:
+            raise ValueError('keep_noise without a mask')
+        st = self._plan_for(obj_embed, triples, clip=bool(clip_denoised), keep=mask is not None)
         O, D = st['x'].shape
         n_steps = self.T if n_steps is None else n_steps
+        if mask is not None:
+            self._fill_keep(st, x0, mask, keep_noise)
         if noise is None:
             st['noise'].normal_()
         else:
             st['noise'][:noise.shape[0]].copy_(noise.to(self.device))
         st['x'].copy_(st['noise'][0])
+        if mask is not None and n_steps > 0:
+            self._prime_keep(st)
         st['plan'].sample(st['step'], 0, n_steps, use_graph=use_graph)
         return st['x'].clone()
 
@@ -509,23 +573,34 @@ def keep_selection(keep_nodes, n_objects):
 
 
 def sample_layout_and_shape(lay, shp, obj_embed, triples, uc, c=None, layout_noise=None, shape_noise=None, use_graph=True,
-                            x0=None, mask=None, keep_noise=None):
+                            x0=None, mask=None, keep_noise=None, box_x0=None, box_mask=None, box_keep_noise=None):
     """Both sampling loops of one scene (EchoScene.py:402-419 runs them back to back) as ONE replayed hipGraph: every replay = one
     DDIM shape step on the main branch and ``T_layout // S_shape`` (= 10) ancestral layout steps on a parallel branch
     (plan.combine_plans), so the latency-bound layout chain -- 131 launches of 32 workgroups per step -- runs inside the gaps
     of the MFMA-bound shape step instead of after it (measured on the bench: 24.3 -> 23.0 ms per full step, i.e. the layout
     step disappears).  Left-over layout steps (T not a multiple of S) run afterwards.  Returns (boxes x_0 [O, 8], latents z_0).
-    ``x0`` / ``mask`` / ``keep_noise``: the masked shape loop (ShapeDenoiser.sample)."""
+    ``x0`` / ``mask`` / ``keep_noise``: the masked shape loop (ShapeDenoiser.sample).  ``box_x0`` / ``box_mask`` / ``box_keep_noise``:
+    the masked layout loop (LayoutDenoiser.sample) -- its keep plan is then the side branch of the fused graph and runs the left-over
+    steps; the two families are independent of each other."""
     from .plan import combine_plans
+    if (box_mask is None) != (box_x0 is None):
+        raise ValueError('the masked layout loop needs both box_x0 and box_mask')
+    if box_mask is None and box_keep_noise is not None:
+        raise ValueError('box_keep_noise without a box_mask')
     if shp.world != 1:
-        return lay.sample(obj_embed, triples, noise=layout_noise, use_graph=use_graph), \
+        return lay.sample(obj_embed, triples, noise=layout_noise, use_graph=use_graph, x0=box_x0, mask=box_mask,
+                          keep_noise=box_keep_noise), \
             shp.sample(uc, triples, noise1=shape_noise, c=c, use_graph=use_graph, x0=x0, mask=mask, keep_noise=keep_noise)
-    st = lay._plan_for(obj_embed, triples)
+    st = lay._plan_for(obj_embed, triples, keep=box_mask is not None)
+    if box_mask is not None:
+        lay._fill_keep(st, box_x0, box_mask, box_keep_noise)
     if layout_noise is None:
         st['noise'].normal_()
     else:
         st['noise'][:layout_noise.shape[0]].copy_(layout_noise.to(lay.device))
     st['x'].copy_(st['noise'][0])
+    if box_mask is not None:
+        lay._prime_keep(st)
     ss = shp._plan_for(uc, triples, c, keep=mask is not None)
     if mask is not None:
         shp._fill_keep(ss, x0, mask, keep_noise)

@@ -88,6 +88,14 @@ class LayoutSchedule:
         tab = torch.stack([srac, srm1, c1, c2, sigma], dim=1)               # indexed by t
         self.timesteps = np.arange(time_num - 1, -1, -1)                     # iteration order
         self.coef = tab[torch.from_numpy(self.timesteps.copy())].contiguous()   # [T, 5] by iteration
+        # masked loop (keep given boxes): q_sample's two factors per iteration (GaussianDiffusion.q_sample, diffusion_ddpm.py:191-201) --
+        # the reference's own tables, the square roots of the fp32 alphas_cumprod (:147-148).  A table of its own: ``coef`` stays as it is.
+        # (torch.sqrt on fp32, the reference's own op: on builds that route it through a vector math library its last bit can differ
+        #  between hosts, as for ``coef`` above -- whoever restates q_sample takes the factors from THIS table)
+        self.sqrt_alphas_cumprod = torch.sqrt(ac).float()
+        self.sqrt_one_minus_alphas_cumprod = torch.sqrt(1.0 - ac).float()
+        tsi = torch.from_numpy(self.timesteps.copy())
+        self.keep_tab = torch.stack([self.sqrt_alphas_cumprod[tsi], self.sqrt_one_minus_alphas_cumprod[tsi]], dim=1).contiguous()   # [T, 2] by iteration
 
 
 class ShapeSchedule:

@@ -231,6 +231,51 @@ typedef struct es_blend_args {
     int32_t O, n;           /* objects, floats per object (n % 4 == 0)                          */
 } es_blend_args;
 int es_ddim_blend(const es_blend_args* args, es_stream stream);
+/* Masked ancestral loop of the layout branch (keep given boxes while the other nodes are placed around them).  The reference's layout
+ * GaussianDiffusion has no masked loop; the definition is the one its shape sampler uses (DDIMSampler.ddim_sampling, samplers/ddim.py:
+ * 160-163) carried over to p_sample_loop_sg (diffusion_ddpm.py:330-345) with GaussianDiffusion.q_sample (:191-201): before the denoiser
+ * of iteration i (t = T-1-i) runs, the row of every kept node is sqrt_alphas_cumprod[t] * x0 + sqrt_one_minus_alphas_cumprod[t] *
+ * keep_noise[i] -- two fp32 products and one sum, no contraction; tab[i] = those two factors (diffusion_ddpm.py:147-148: the square roots
+ * of the fp32 alphas_cumprod).  A blend launch in front of every step (the shape branch's arrangement) would cost the latency-bound
+ * layout step a launch, so the blend is folded into the step's LAST launch: es_ddpm_update_keep is es_ddpm_update on the rows with
+ * mask 0 (same expressions, same bits; clip_x0 applies to them only) and writes, into the rows with mask 1, what the NEXT iteration's
+ * denoiser has to read:
+ *     step + 1 <  n_tab:  x[o, :] = tab[2 (step+1)] * x0[o, :] + tab[2 (step+1) + 1] * keep_noise[step+1][o, :]
+ *     step + 1 == n_tab:  x[o, :] = x0[o, :]                 (after the last iteration the kept rows are x0 itself, bit for bit)
+ * A kept element reads neither eps nor noise; rows with mask 0 of x0 / keep_noise are never read; row step + 1 of tab / keep_noise is
+ * read only when step + 1 < n_tab.  The rows of x_T are primed once before the loop with es_ddim_blend (the same arithmetic at
+ * n = row).  A loop stopped early (fewer than n_tab iterations) therefore leaves the kept rows at the NEXT timestep's forward-noised
+ * value, not at x0.  n <= 4096: one workgroup, which also advances the step counter; beyond: one workgroup per 256 elements and the
+ * separate step increment, as es_ddpm_update. */
+typedef struct es_ddpm_keep_args {
+    float* x;               /* [n] state, updated in place                                      */
+    const float* eps;       /* [n] network output (slab tensor as in es_update_args)            */
+    int32_t eps_nslab, eps_slab_stride;
+    const float* noise;     /* noise + (*step) * noise_stride: this step's draw (generated rows) */
+    int32_t noise_stride;
+    const float* coef;      /* [n_tab][coef_stride] (the five numbers of es_ddpm_update)        */
+    int32_t coef_stride;
+    int32_t* step;
+    int32_t n;
+    int32_t inc_step;
+    int32_t clip_x0;        /* generated rows only                                              */
+    const float* x0;        /* [n] the kept nodes' rows (rows with mask == 0 are not read)      */
+    const float* mask;      /* [n / row] 0 = generate, 1 = keep                                 */
+    const float* keep_noise;/* [n_tab][keep_noise_stride]: q_sample's draw of iteration i at row i */
+    int32_t keep_noise_stride;
+    const float* tab;       /* [n_tab][2]                                                       */
+    int32_t n_tab;          /* iterations of the schedule                                       */
+    int32_t row;            /* floats per object (n % row == 0)                                 */
+} es_ddpm_keep_args;
+int es_ddpm_update_keep(const es_ddpm_keep_args* args, es_stream stream);
+/* The inverse of es_box_postprocess: metric boxes -> the normalised rows of the layout state, so that a box of a dataset scene or of a
+ * de-normalised result can be kept.  scale_box_params (helpers/util.py:516-532; ncol = 6: sizes | translations, ncol = 7: also column
+ * 6, a metric angle, its ``angle`` flag :528-530): out[o, c] = 2 (boxes[o, c] - lo_c) / (hi_c - lo_c) - 1, and preprocess_angle2sincos
+ * (:534-540): sincos_out[o] = (sin, cos)(angles[o]).  stats = the 14 numbers of the dataset's boxes_centered_stats file as DOUBLES (the
+ * reference computes on float64 statistics); everything is evaluated in double and rounded to fp32 once.  boxes [O, ld], out [O, out_ld]
+ * (may alias boxes), angles [O], sincos_out [O, 2]; either half may be skipped with NULL pointers. */
+int es_box_prescale(const float* boxes, int ld, int ncol, const float* angles, const double* stats, float* out, int out_ld,
+                    float* sincos_out, int O, es_stream stream);
 
 /* ------------------------------------------------------------------------------------------
  * "volume" path -- the 3-D latent-SDF UNet (openai_model_3d.py:816-863).  Activations are
@@ -446,7 +491,9 @@ enum {
     ES_OP_FORK = 13, ES_OP_JOIN = 14, ES_OP_ROWSEL = 15,
     ES_OP_CONV_F32 = 16, ES_OP_ATTN_F32 = 17,     /* the fp32-operand validation route: es_conv_f32 / es_attention_f32 on the same argument structs */
     ES_OP_DDIM_BLEND = 18,                        /* es_ddim_blend (es_blend_args): the masked-DDIM blend in front of a step's denoiser */
-    ES_OP_CONV_C1 = 19                            /* es_conv_c1_f32 (es_conv_c1_args): the VQ-VAE encoder's one-channel conv_in */
+    ES_OP_CONV_C1 = 19,                           /* es_conv_c1_f32 (es_conv_c1_args): the VQ-VAE encoder's one-channel conv_in */
+    ES_OP_DDPM_KEEP = 21                          /* es_ddpm_update_keep (es_ddpm_keep_args): the layout update that also carries the kept rows.
+                                                     (20 stays unassigned: es_op_pointer_offsets(20) is pinned to "unknown kind") */
 };
 /* Row select: out[r, 0..n) = table[*step, 0..n) for r < rows.  The timestep-dependent but node-independent products of a
  * denoiser (time MLP, all ResBlock emb projections, box/shape time embedding) are tabulated once per schedule
@@ -472,6 +519,7 @@ typedef struct es_op {
         es_linear_args linear; es_update_args update; es_copy_args copy; es_conv_args conv;
         es_gn_args gn; es_ln_args ln; es_attn_args attn; es_geglu_args geglu; es_tocl_args tocl;
         es_stem_args stem; es_vq_args vq; es_rowsel_args rowsel; es_blend_args blend; es_conv_c1_args conv_c1;
+        es_ddpm_keep_args keep;
     } u;
 } es_op;
 
@@ -534,6 +582,8 @@ int es_sampler_run(es_plan* plan, int32_t* step, int first_step, int n_steps, in
  * hipMalloc, uploads the contents, rebases the pointers and creates the plan.  Named regions give the caller its I/O:
  *   layout model:  "x" [O,8] state, "noise" [T+1,O,8] (row 0 = x_T, row 1+i = draw of iteration i), "step" int32
  *   shape model :  "x" [O,3,16,16,16] latents, "step" int32
+ *   layout model saved with keep=True (the masked loop, es_layout_sample_keep): also "x0" [O,8], "mask" [O], "knoise" [T,O,8]
+ *                  (q_sample's draws, row i = iteration i) and "ktab" [T,2] (es_ddpm_keep_args.tab)
  *   both loops  :  "coef" = the schedule's coefficient table [n_steps][coef_stride]: es_model_run / es_layout_sample / es_shape_sample
  *                  refuse to run past its last row
  *   vq model    :  "z" [O,3,16,16,16] input latents, "sdf" [O,1,64,64,64] output
@@ -555,6 +605,12 @@ int es_model_run(es_model* model, int first_step, int n_steps, es_stream stream)
 /* GaussianDiffusion.p_sample_loop_sg (diffusion_ddpm.py:330-345): noise [n_rows >= n_steps + 1][O*8] device fp32 (row 0 = x_T);
  * x_out [O*8] device fp32 = x after n_steps ancestral steps */
 int es_layout_sample(es_model* model, const float* noise, int noise_rows, int n_steps, float* x_out, es_stream stream);
+/* es_layout_sample with kept boxes (a model saved with keep=True): x0 [O*8], mask [O] (0 / 1) and keep_noise [min(n_steps + 1, T)][O*8]
+ * (row i = q_sample's draw of iteration i) are copied into the model's regions, x_T = noise row 0 with its kept rows primed to q_sample(x0, T-1, keep_noise[0]) (one es_ddim_blend
+ * launch), then n_steps replays.  After all T iterations the kept rows of x_out are x0 bit for bit; after fewer they hold the next
+ * timestep's forward-noised value.  Refuses to run past the model's schedule. */
+int es_layout_sample_keep(es_model* model, const float* noise, int noise_rows, int n_steps, const float* x0, const float* mask,
+                          const float* keep_noise, float* x_out, es_stream stream);
 /* DDIMSampler.ddim_sampling (samplers/ddim.py:127-181): z_T [O,3,16,16,16] device fp32 -> z_out after n_steps DDIM steps */
 int es_shape_sample(es_model* model, const float* z_T, int n_steps, float* z_out, es_stream stream);
 /* VQVAE.decode_no_quant (vqvae_networks/network.py:95-103): z [O,3,16,16,16] -> sdf_out [O,1,64,64,64], device fp32 */
