@@ -75,6 +75,9 @@ static int dispatch(const es_op& op, hipStream_t s) {
         case ES_OP_DDIM_BLEND: return es_ddim_blend(&op.u.blend, s);
         case ES_OP_CONV_C1: return es_conv_c1_f32(&op.u.conv_c1, s);
         case ES_OP_DDPM_KEEP: return es_ddpm_update_keep(&op.u.keep, s);
+        case ES_OP_PLMS: return es_plms_update(&op.u.plms, s);
+        case ES_OP_PLMS_FIRST_A: return es_plms_first_a(&op.u.plms, s);
+        case ES_OP_PLMS_FIRST_B: return es_plms_first_b(&op.u.plms, s);
         default: es_set_error("plan: unknown op kind %d", op.kind); return 3;
     }
 }
@@ -292,6 +295,9 @@ extern "C" int es_op_pointer_offsets(int kind, size_t* out, int cap) {
         case ES_OP_DDPM_KEEP:
             v = {ES_PTR(keep.x), ES_PTR(keep.eps), ES_PTR(keep.noise), ES_PTR(keep.coef), ES_PTR(keep.step), ES_PTR(keep.x0), ES_PTR(keep.mask),
                  ES_PTR(keep.keep_noise), ES_PTR(keep.tab)};
+            break;
+        case ES_OP_PLMS: case ES_OP_PLMS_FIRST_A: case ES_OP_PLMS_FIRST_B:
+            v = {ES_PTR(plms.x), ES_PTR(plms.eps), ES_PTR(plms.coef), ES_PTR(plms.step), ES_PTR(plms.ring), ES_PTR(plms.xsave)};
             break;
         case ES_OP_FORK: case ES_OP_JOIN: break;
         default: return -1;

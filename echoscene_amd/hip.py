@@ -114,6 +114,14 @@ class BlendArgs(C.Structure):
     _fields_ = [('x', C.c_void_p), ('x0', C.c_void_p), ('mask', C.c_void_p), ('noise', C.c_void_p), ('noise_stride', C.c_int32),
                 ('tab', C.c_void_p), ('step', C.c_void_p), ('O', C.c_int32), ('n', C.c_int32)]
 
+OP_PLMS, OP_PLMS_FIRST_A, OP_PLMS_FIRST_B = 23, 24, 25     # PLMS sampling of the shape branch (csrc/es_plms.hip); 22 stays unassigned
+
+
+class PlmsArgs(C.Structure):
+    _fields_ = [('x', C.c_void_p), ('eps', C.c_void_p), ('eps_nslab', C.c_int32), ('eps_slab_stride', C.c_int32),
+                ('coef', C.c_void_p), ('coef_stride', C.c_int32), ('n', C.c_int32), ('step', C.c_void_p),
+                ('inc_step', C.c_int32), ('ring_stride', C.c_int32), ('ring', C.c_void_p), ('xsave', C.c_void_p)]
+
 
 class DdpmKeepArgs(C.Structure):
     _fields_ = [('x', C.c_void_p), ('eps', C.c_void_p), ('eps_nslab', C.c_int32), ('eps_slab_stride', C.c_int32),
@@ -133,7 +141,7 @@ class _OpU(C.Union):
     _fields_ = [('linear', LinearArgs), ('update', UpdateArgs), ('copy', CopyArgs), ('conv', ConvArgs),
                 ('gn', GNArgs), ('ln', LNArgs), ('attn', AttnArgs), ('geglu', GegluArgs), ('tocl', ToClArgs),
                 ('stem', StemArgs), ('vq', VQArgs), ('rowsel', RowSelArgs), ('blend', BlendArgs), ('conv_c1', ConvC1Args),
-                ('keep', DdpmKeepArgs)]
+                ('keep', DdpmKeepArgs), ('plms', PlmsArgs)]
 
 
 class Op(C.Structure):
@@ -174,6 +182,9 @@ EXPORTS = {
     'es_ddim_blend': (C.c_int, [C.POINTER(BlendArgs), C.c_void_p]),
     'es_conv_c1_f32': (C.c_int, [C.POINTER(ConvC1Args), C.c_void_p]),
     'es_ddpm_update_keep': (C.c_int, [C.POINTER(DdpmKeepArgs), C.c_void_p]),
+    'es_plms_update': (C.c_int, [C.POINTER(PlmsArgs), C.c_void_p]),
+    'es_plms_first_a': (C.c_int, [C.POINTER(PlmsArgs), C.c_void_p]),
+    'es_plms_first_b': (C.c_int, [C.POINTER(PlmsArgs), C.c_void_p]),
     'es_box_prescale': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                   C.c_void_p]),
     'es_box_postprocess': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_float,

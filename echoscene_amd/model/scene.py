@@ -128,13 +128,16 @@ class EchoToShape(object):
         self.ddim_steps = 100                           # hard-coded by the reference (echo2shape.py:118)
         if opt.misc.get('debug', 0) == 1:
             self.ddim_steps = 7
+        self.shape_sampler = 'ddim'                     # 'plms': the reference's PLMSSampler (samplers/plms.py) on the same schedule
         self.uc_scale = 3.0                             # read but never applied (ddim.py:207-228)
         self._den = None
+        self._dens = {}
         self._dec = None
         self.triples = None
 
     def invalidate(self):
         self._den = None
+        self._dens = {}
         self._dec = None
         self._enc = None
 
@@ -150,12 +153,34 @@ class EchoToShape(object):
     def forward(self, *a, **k):
         raise NotImplementedError('training (EchoToShape.forward / p_losses) is out of scope of this build')
 
-    def _denoiser(self, ddim_eta=0.0):
-        if self._den is None or self._den.S != self._expected_steps() or self._den.ddim_eta != float(ddim_eta):
-            from ..samplers import ShapeDenoiser
-            self._den = ShapeDenoiser(self.df, self.df_conf.model.params, ddim_steps=self.ddim_steps,
-                                      device=_hip_device(_dev(self.df)), z_shape=self.z_shape, ddim_eta=ddim_eta)
-        return self._den
+    def _denoiser(self, ddim_eta=0.0, sampler=None, steps=None):
+        """``sampler`` / ``steps``: ``shape_sampler=`` / ``shape_steps=`` of the sampling calls (None: the attributes ``shape_sampler`` /
+        ``ddim_steps``).  The default combination lives in ``_den`` as it always has; another (sampler, step count) gets a denoiser of
+        its own -- its schedule tables and plans -- that shares the packed weights; the two most recent of those stay resident."""
+        sampler = self.shape_sampler if sampler is None else sampler
+        steps = self.ddim_steps if steps is None else int(steps)
+        from ..samplers import ShapeDenoiser
+        from ..schedules import SHAPE_SAMPLERS
+        if sampler not in SHAPE_SAMPLERS:
+            raise ValueError('shape_sampler must be one of %s, got %r' % (SHAPE_SAMPLERS, sampler))
+        if steps < 1:
+            raise ValueError('shape_steps must be a positive step count, got %r' % (steps,))
+        if sampler == 'ddim' and steps == self.ddim_steps:
+            if self._den is None or self._den.S != self._expected_steps() or self._den.ddim_eta != float(ddim_eta) \
+                    or self._den.sampler != 'ddim':
+                self._den = ShapeDenoiser(self.df, self.df_conf.model.params, ddim_steps=self.ddim_steps,
+                                          device=_hip_device(_dev(self.df)), z_shape=self.z_shape, ddim_eta=ddim_eta)
+            return self._den
+        key = (sampler, steps, float(ddim_eta))
+        den = self._dens.get(key)
+        if den is None:
+            w = self._den.w if self._den is not None else next((d.w for d in self._dens.values()), None)
+            den = ShapeDenoiser(self.df, self.df_conf.model.params, ddim_steps=steps, device=_hip_device(_dev(self.df)),
+                                z_shape=self.z_shape, ddim_eta=ddim_eta, sampler=sampler, weights=w)
+            while len(self._dens) >= 2:
+                self._dens.pop(next(iter(self._dens)))
+            self._dens[key] = den
+        return den
 
     def _expected_steps(self):
         return len(range(0, self.df_conf.model.params.timesteps,
@@ -190,13 +215,15 @@ class EchoToShape(object):
         return self._dec
 
     @torch.no_grad()
-    def rel2shape(self, data, ddim_eta=0.0, noise=None, sync=True, step_noise=None):
+    def rel2shape(self, data, ddim_eta=0.0, noise=None, sync=True, step_noise=None, *, shape_sampler=None, shape_steps=None):
         """echo2shape.py:484-525: one latent noise shared by all objects, 100-step DDIM (eta 0, no CFG),
         then VQ-VAE decode_no_quant -> SDF [O,1,64,64,64].  ``noise`` f32[1,C,D,H,W] replaces the
-        reference's wall-clock seeded draw (``torch.manual_seed(int(time.time()))``, :502)."""
+        reference's wall-clock seeded draw (``torch.manual_seed(int(time.time()))``, :502).
+        ``shape_sampler`` ('ddim' | 'plms') / ``shape_steps`` (keyword-only; None: the attributes ``shape_sampler`` / ``ddim_steps``):
+        the sampler of the shape loop and its step count -- 'plms' is the reference's PLMSSampler, S + 1 evaluations for S steps."""
         self.switch_eval()
         self.set_input(data)
-        den = self._denoiser(ddim_eta)             # ddim_eta != 0: sigma_t * randn per step and object (``step_noise`` f32[S,O,C,D,H,W] or drawn)
+        den = self._denoiser(ddim_eta, shape_sampler, shape_steps)             # ddim_eta != 0: sigma_t * randn per step and object (``step_noise`` f32[S,O,C,D,H,W] or drawn)
         if noise is None:
             g = torch.Generator(device=den.device).manual_seed(int(time.time()))
             noise = torch.randn((1,) + tuple(self.z_shape), device=den.device, generator=g)
@@ -424,17 +451,17 @@ class Sg2ScDiffModel(_SceneModel):
         torch.cuda.synchronize()
         return o.t.unsqueeze(1)
 
-    def _shapes(self, gen_shape, dec_objs, dec_triples, obj_embed_, latent, shape_noise=None):
+    def _shapes(self, gen_shape, dec_objs, dec_triples, obj_embed_, latent, shape_noise=None, shape_sampler=None, shape_steps=None):
         if not gen_shape:
             return None
         uc = self._rel_s(obj_embed_)
         c = self._rel_s(latent)
         return self.ShapeDiff.rel2shape({'obj_cat': dec_objs, 'triples': dec_triples, 'c_s': c, 'uc_s': uc},
-                                        noise=shape_noise)
+                                        noise=shape_noise, shape_sampler=shape_sampler, shape_steps=shape_steps)
 
     def _layout_and_shapes(self, gen_shape, dec_objs, dec_triples, obj_embed_, latent, layout_noise, shape_noise,
                            keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None, keep_boxes=None,
-                           keep_box_noise=None):
+                           keep_box_noise=None, shape_sampler=None, shape_steps=None):
         """The two loops only share the setup (the reference runs them back to back, EchoScene.py:402-419).  Here they are
         ONE replayed hipGraph: each replay is a DDIM shape step with ten ancestral layout steps on a parallel branch
         (samplers.sample_layout_and_shape), then the VQ-VAE decode.
@@ -445,7 +472,11 @@ class Sg2ScDiffModel(_SceneModel):
 
         ``keep_box_nodes`` / ``keep_boxes`` (box-preserving sampling, independent of the above; with or without gen_shape): the listed
         nodes keep the normalised boxes the caller hands in (_box_keep) -- the masked ancestral layout loop -- and the returned
-        sizes / translations / angles rows of those nodes are the caller's numbers bit for bit."""
+        sizes / translations / angles rows of those nodes are the caller's numbers bit for bit.
+
+        ``shape_sampler`` / ``shape_steps``: sampler ('ddim' | 'plms') and step count of the shape loop (None: ``ShapeDiff.shape_sampler`` /
+        ``ShapeDiff.ddim_steps``); they combine freely with both keep families.  With ``gen_shape=False`` no shape loop runs and they
+        are not looked at (unlike ``keep_nodes``, which names inputs that would be dropped, they only choose how a loop would run)."""
         if (keep_nodes is None) != (keep_sdfs is None):
             raise ValueError('keep_nodes and keep_sdfs go together')
         if not gen_shape:
@@ -460,7 +491,7 @@ class Sg2ScDiffModel(_SceneModel):
         L.set_input({'preds': dec_triples, 'box': None, 'uc_b': obj_embed_, 'c_b': latent, 'obj_id_to_scene': None})
         S.switch_eval()
         S.set_input({'obj_cat': dec_objs, 'triples': dec_triples, 'c_s': c, 'uc_s': uc})
-        sden = S._denoiser()
+        sden = S._denoiser(0.0, shape_sampler, shape_steps)
         need_c = S.df.conditioning_key == 'concat' or not S.df.diffusion_net.messsage_passing
         if shape_noise is None:       # the reference seeds this draw from the wall clock (echo2shape.py:502)
             g = torch.Generator(device=sden.device).manual_seed(int(time.time()))
@@ -496,17 +527,18 @@ class Sg2ScDiffModel(_SceneModel):
     @torch.no_grad()
     def sample(self, dec_objs, dec_triplets, dec_text_feat, dec_rel_feat, gen_shape=False, layout_noise=None,
                shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None,
-               keep_boxes=None, keep_box_noise=None):
+               keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None):
         """EchoScene.py:388-420.  ``keep_nodes`` / ``keep_sdfs`` and ``keep_box_nodes`` / ``keep_boxes`` (keyword-only): see
         _layout_and_shapes."""
         oe, _, latent_m = self._setup(dec_objs, dec_triplets, dec_text_feat, dec_rel_feat,
                                       dec_objs, dec_triplets, dec_text_feat, dec_rel_feat)
         sdf, boxes = self._layout_and_shapes(gen_shape, dec_objs, dec_triplets, oe, latent_m, layout_noise, shape_noise,
-                                             keep_nodes, keep_sdfs, keep_noise, keep_box_nodes, keep_boxes, keep_box_noise)
+                                             keep_nodes, keep_sdfs, keep_noise, keep_box_nodes, keep_boxes, keep_box_noise,
+                                             shape_sampler, shape_steps)
         return {'shapes': sdf}, boxes
 
     def _edited(self, enc, dec, touched, added, gen_shape, layout_noise, shape_noise, keep_nodes=None, keep_sdfs=None,
-                keep_noise=None, keep_box_nodes=None, keep_boxes=None, keep_box_noise=None):
+                keep_noise=None, keep_box_nodes=None, keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None):
         oe, latent, latent_m = self._setup(*enc, *dec, change_rows=touched, added_rows=added)
         if not self.replace_all_latent:
             latent = latent.clone()
@@ -516,7 +548,8 @@ class Sg2ScDiffModel(_SceneModel):
         else:
             latent = latent_m
         sdf, boxes = self._layout_and_shapes(gen_shape, dec[0], dec[1], oe, latent, layout_noise, shape_noise,
-                                             keep_nodes, keep_sdfs, keep_noise, keep_box_nodes, keep_boxes, keep_box_noise)
+                                             keep_nodes, keep_sdfs, keep_noise, keep_box_nodes, keep_boxes, keep_box_noise,
+                                             shape_sampler, shape_steps)
         keep = torch.ones(len(boxes['translations']), 1, device=oe.device)
         for t in touched:
             if 0 <= int(t) < keep.shape[0]:
@@ -527,18 +560,18 @@ class Sg2ScDiffModel(_SceneModel):
     def sample_with_changes(self, enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triplets,
                             dec_text_feat, dec_rel_feat, manipulated_nodes, gen_shape=False, layout_noise=None,
                             shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None,
-               keep_boxes=None, keep_box_noise=None):
+               keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None):
         """EchoScene.py:422-472.  ``keep_nodes`` / ``keep_sdfs`` (keyword-only): see _layout_and_shapes."""
         return self._edited((enc_objs, enc_triples, enc_text_feat, enc_rel_feat),
                             (dec_objs, dec_triplets, dec_text_feat, dec_rel_feat),
                             list(manipulated_nodes), [], gen_shape, layout_noise, shape_noise, keep_nodes, keep_sdfs, keep_noise,
-                            keep_box_nodes, keep_boxes, keep_box_noise)
+                            keep_box_nodes, keep_boxes, keep_box_noise, shape_sampler, shape_steps)
 
     @torch.no_grad()
     def sample_with_additions(self, enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triplets,
                               dec_text_feat, dec_rel_feat, missing_nodes, gen_shape=False, layout_noise=None,
                               shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None,
-               keep_boxes=None, keep_box_noise=None):
+               keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None):
         """EchoScene.py:474-532: zero rows inserted at ``missing_nodes[i] + i``; note the reference draws the
         change noise for rows listed in ``missing_nodes`` (:489-494) but splices / masks ``nodes_added``."""
         added = [m + i for i, m in enumerate(missing_nodes)]
@@ -552,7 +585,8 @@ class Sg2ScDiffModel(_SceneModel):
         else:
             latent = latent_m
         sdf, boxes = self._layout_and_shapes(gen_shape, dec_objs, dec_triplets, oe, latent, layout_noise, shape_noise,
-                                             keep_nodes, keep_sdfs, keep_noise, keep_box_nodes, keep_boxes, keep_box_noise)
+                                             keep_nodes, keep_sdfs, keep_noise, keep_box_nodes, keep_boxes, keep_box_noise,
+                                             shape_sampler, shape_steps)
         keep = torch.ones(len(boxes['translations']), 1, device=oe.device)
         for t in added:
             keep[t] = 0
@@ -696,6 +730,8 @@ class SGDiff(nn.Module):
     def _no_keep_without_shapes(self, kw):
         if self.type_ == 'echolayout' and any(kw.get(k) is not None for k in ('keep_nodes', 'keep_sdfs', 'keep_noise')):
             raise ValueError("keep_nodes / keep_sdfs keep SHAPES; an 'echolayout' model has no shape branch")
+        if self.type_ == 'echolayout' and any(kw.get(k) is not None for k in ('shape_sampler', 'shape_steps')):
+            raise ValueError("shape_sampler / shape_steps choose the sampler of the SHAPE loop; an 'echolayout' model has no shape branch")
 
     @staticmethod
     def _box_kw(kw):
@@ -711,7 +747,11 @@ class SGDiff(nn.Module):
         the rows this call returns (postprocess.scale_box_params / preprocess_angle2sincos bring metric boxes there) -- while the other
         nodes are placed in their context (the masked ancestral loop); the returned rows of the kept nodes are the caller's numbers
         bit for bit.  ``keep_box_noise`` f32 [T, O, 8]: the forward-noising draws (None: drawn on the device).  Independent of
-        ``keep_nodes`` / ``keep_sdfs``; also on the two editing calls."""
+        ``keep_nodes`` / ``keep_sdfs``; also on the two editing calls.
+        ``shape_sampler`` ('ddim' | 'plms') + ``shape_steps`` (keyword-only; None: ``diff.ShapeDiff.shape_sampler`` / ``.ddim_steps``, i.e.
+        DDIM with 100 steps): sampler and step count of the shape loop.  'plms' is the reference's PLMSSampler (pseudo linear multistep,
+        S + 1 denoiser evaluations for S steps; eta = 0 and at least two timesteps, else ValueError); it combines with both keep
+        families.  Also on the two editing calls.  With ``gen_shape=False`` there is no shape loop and they have no effect."""
         self._no_keep_without_shapes(noise)
         if self.type_ == 'echolayout':
             return self.diff.sampleBoxes(dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat,

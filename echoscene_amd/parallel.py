@@ -56,6 +56,8 @@ def sharded_ddim_loop(backend, num_objects, n_steps, world, group=None):
         step(i, codes_all)    -> advance this rank's latents by DDIM iteration i given all objects' codes
         latents_local()       -> [O_local, C, D, H, W]
         gather_buffers()      -> optional: pre-allocated (send block, receive buffer) of the exchange
+        passes(i)             -> optional: evaluations of iteration i (PLMS: 2 in iteration 0); pass p > 0 is called as
+                                 codes_local(i, p) / step(i, codes_all, p)
     Per step on the HIP path: graph launch (stem), all-gather of [block, 64] floats per rank, graph launch (rest) -- no allocation,
     no torch op in between; with ES_STEP_GRAPH=1 and every rank able to capture it (a collective decision, backend.step_graph)
     ONE captured graph = stem ops, the RCCL all-gather, everything else.  Returns the full latents [O, C, D, H, W] on every
@@ -70,12 +72,19 @@ def sharded_ddim_loop(backend, num_objects, n_steps, world, group=None):
             g.replay()
         zl = backend.latents_local()
         return all_gather_rows(zl, num_objects, world, group) if world > 1 else zl
+    passes = getattr(backend, 'passes', None)
     for i in range(n_steps):
-        cl = backend.codes_local(i)
-        if exchange:
-            ca = all_gather_rows(cl, num_objects, world, group, out=bufs[1] if bufs else None)
-        else:
-            ca = cl
-        backend.step(i, ca)
+        # a PLMS backend evaluates the denoiser twice in iteration 0 (backend.passes(0) == 2): a second stem -> all-gather -> rest, which
+        # every rank joins -- S + 1 all-gathers for S iterations, also on a rank that owns no object
+        for p in range(passes(i) if passes is not None else 1):
+            cl = backend.codes_local(i, p) if p else backend.codes_local(i)
+            if exchange:
+                ca = all_gather_rows(cl, num_objects, world, group, out=bufs[1] if bufs else None)
+            else:
+                ca = cl
+            if p:
+                backend.step(i, ca, p)
+            else:
+                backend.step(i, ca)
     zl = backend.latents_local()
     return all_gather_rows(zl, num_objects, world, group) if world > 1 else zl

@@ -625,6 +625,8 @@ def count_launches(ops):
             n += 1                           # (the one-workgroup DDPM update advances the step counter itself)
         if op.kind == hip.OP_DDPM_KEEP and op.u.keep.inc_step and op.u.keep.n > 4096:
             n += 1                           # (es_ddpm_update_keep: as OP_DDPM)
+        if (op.kind == hip.OP_PLMS and op.u.plms.inc_step) or op.kind == hip.OP_PLMS_FIRST_A:
+            n += 1                           # (the PLMS update's step increment; first-a sets the counter to 1)
         i += k
     return n
 

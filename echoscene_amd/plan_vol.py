@@ -507,6 +507,30 @@ class VolBuilderMixin:
         self.keep += [x0, mask, noise, tab]
         return self._push(hip.OP_DDIM_BLEND, 'blend', a)
 
+    def plms(self, kind, x, eps, coef, step, ring, xsave, inc_step=True, push=True):
+        """a PLMS sampler op (es_plms_update / es_plms_first_a / es_plms_first_b, ``kind`` = hip.OP_PLMS*): x [O, ...], eps a tensor or
+        a (slab) View, coef the DDIM table [S, 4], ring [3, n] the last three eps, xsave [n] (first iteration only).  ``push=False``: the op is returned, not
+        appended (the first-iteration ops go into a plan of their own)"""
+        a = hip.PlmsArgs()
+        if isinstance(eps, View):
+            assert eps.ld == eps.width and eps.col == 0
+            a.eps, a.eps_nslab, a.eps_slab_stride = eps.ptr, eps.nslab, eps.slab_stride
+            self.keep.append(eps.t)
+        else:
+            a.eps = eps.data_ptr()
+        a.x, a.n = x.data_ptr(), x.numel()
+        a.coef, a.coef_stride = coef.data_ptr(), coef.shape[1]
+        a.step, a.inc_step = step.data_ptr(), 1 if (inc_step and kind == hip.OP_PLMS) else 0
+        assert ring.shape[0] == 3 and ring.shape[1] >= x.numel() and xsave.numel() == x.numel() and coef.shape[1] == 4
+        a.ring, a.ring_stride, a.xsave = ring.data_ptr(), ring.shape[1], xsave.data_ptr()
+        self.keep += [ring, xsave, coef]
+        if not push:
+            op = Op()
+            op.kind, op.lane = kind, 0
+            op.u.plms = a
+            return op
+        return self._push(kind, 'plms', a)
+
     def stem(self, x, w, scratch, out, O, cin=3, ostride=0):
         a = StemArgs()
         a.x = x.data_ptr()
@@ -800,7 +824,7 @@ def emit_unet3d_step(b, w, g, x, uc_dev, temb, step, eps_out, dims=(16, 16, 16),
     return objbuf
 
 
-for _n in ('_push', 'conv', '_conv32', 'split3', 'conv_gn_intermediate', '_rowgroup_producer', '_rowgroup_stats', 'groupnorm', 'layernorm', 'attention', 'geglu', 'to_cl', 'stem', 'conv_c1', 'blend'):
+for _n in ('_push', 'conv', '_conv32', 'split3', 'conv_gn_intermediate', '_rowgroup_producer', '_rowgroup_stats', 'groupnorm', 'layernorm', 'attention', 'geglu', 'to_cl', 'stem', 'conv_c1', 'blend', 'plms'):
     setattr(Builder, _n, getattr(VolBuilderMixin, _n))
 
 

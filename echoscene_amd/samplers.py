@@ -8,7 +8,7 @@ import torch
 from . import hip
 from .plan import (Builder, GraphIndex, View, GCNWeights, UNet1DWeights, emit_gcn, emit_unet1d_step, time_tables)
 from .plan_vol import UNet3DWeights, emit_unet3d_step, VQWeights, emit_vq_decode, VQEncWeights, emit_vq_encode
-from .schedules import LayoutSchedule, ShapeSchedule, timestep_embedding_table
+from .schedules import LayoutSchedule, ShapeSchedule, timestep_embedding_table, SHAPE_SAMPLERS
 
 
 def _cap(n_triples):
@@ -218,7 +218,7 @@ class ShapeDenoiser:
     step as one hipGraph; world > 1 splits each step at the echo all-gather."""
 
     def __init__(self, df, model_params=None, ddim_steps=100, device=None, z_shape=(3, 16, 16, 16), rank=0, world=1,
-                 group=None, deterministic=False, force_exchange=False, precision='fp16', ddim_eta=0.0):
+                 group=None, deterministic=False, force_exchange=False, precision='fp16', ddim_eta=0.0, sampler='ddim', weights=None):
         """``force_exchange``: build the sharded step structure (stem plan -> code exchange -> main plan) even at world == 1 --
         the one-GPU test of the captured RCCL exchange (tests/test_hip_scene.py).
         ``precision``: 'fp16' (product: fp16 MFMA operands, fp32 accumulate) or 'fp32' -- the VALIDATION route: fp32 activations and
@@ -229,21 +229,36 @@ class ShapeDenoiser:
         # 'fp32x' (round 6): fp32 activations, fp32 attention / norms, and every contraction on the f16 matrix pipe with SPLIT operands
         # (x = hi + lo in f16, three partial products accumulated in fp32: plan_vol.PackedConvX3) -- the reference's arithmetic to
         # ~2^-21 per product at 3x the K of the product route, instead of the 1/16 matrix rate of 'fp32'
+        # ``sampler``: 'ddim' (the shipped loop) or 'plms' -- the reference's PLMSSampler (samplers/plms.py) on the SAME schedule and
+        # tables: pseudo linear multistep, S + 1 denoiser evaluations for S iterations (schedules.plms_evaluations), the usual way to halve
+        # the step count of a deterministic sampler.  ``sample(sampler=)`` may override it per call (each sampler has plans of its own).
+        # ``weights``: the packed UNet3DWeights of another ShapeDenoiser of the same network, device and precision (another step count or
+        # sampler does not need a second copy of them)
         if precision not in ('fp16', 'fp32', 'fp32x'):
             raise ValueError("precision must be 'fp16', 'fp32' or 'fp32x'")
+        if sampler not in SHAPE_SAMPLERS:
+            raise ValueError('sampler must be one of %s, got %r' % (SHAPE_SAMPLERS, sampler))
+        self.sampler = sampler
         self.precision = precision
         self.force_exchange = bool(force_exchange)
         self.device = device or torch.device('cuda')
         self.df = df
         net = df.diffusion_net
         self.net = net
-        sd = {k[len('diffusion_net.'):]: v for k, v in state_dict_for(df, self.device).items()}
-        self.w = UNet3DWeights(sd, net, self.device, precision)
+        if weights is not None:
+            if getattr(weights, 'precision', None) != precision:
+                raise ValueError('weights were packed for precision %r, this denoiser asks for %r' % (getattr(weights, 'precision', None), precision))
+            self.w = weights
+        else:
+            sd = {k[len('diffusion_net.'):]: v for k, v in state_dict_for(df, self.device).items()}
+            self.w = UNet3DWeights(sd, net, self.device, precision)
         mp = dict(model_params or {})
         self.ddim_eta = float(ddim_eta)
         self.sched = ShapeSchedule(ddim_steps, mp.get('timesteps', 1000), mp.get('linear_start', 0.00085),
                                    mp.get('linear_end', 0.012), eta=self.ddim_eta)
         self.S = len(self.sched.timesteps)
+        if sampler == 'plms':
+            self._check_plms()
         self.z_shape = tuple(z_shape)
         self.temb = timestep_embedding_table(self.sched.timesteps, net.model_channels).to(self.device)
         self.coef = self.sched.coef.to(self.device)
@@ -262,6 +277,22 @@ class ShapeDenoiser:
         self.tables = time_tables(self.w, self.temb, self.w.shape_t, self.device)
         self._plans, self.max_plans = {}, 2
 
+    def _check_plms(self):
+        """PLMS needs eta = 0 (PLMSSampler.make_schedule raises the same way, plms.py:28-29) and two timesteps: with one, the reference
+        evaluates the denoiser twice at the same t (t_next = t, plms.py:152); that degenerate run is not offered."""
+        if self.ddim_eta != 0.0:
+            raise ValueError('ddim_eta must be 0 for PLMS')
+        if self.S < 2:
+            raise ValueError('PLMS needs at least 2 timesteps (ddim_steps=%d yields %d)' % (self.S, self.S))
+
+    def _sampler_of(self, sampler):
+        sampler = self.sampler if sampler is None else sampler
+        if sampler not in SHAPE_SAMPLERS:
+            raise ValueError('sampler must be one of %s, got %r' % (SHAPE_SAMPLERS, sampler))
+        if sampler == 'plms':
+            self._check_plms()
+        return sampler
+
     def _insert_plan(self, key, st):
         """bounded plan cache: evicting a plan also drops the fused (layout + shape) graph built on it -- each resident plan
         owns its activation buffers, split-K workspace and captured graph (several GB at O = 32)"""
@@ -272,8 +303,12 @@ class ShapeDenoiser:
                 self._fused, self._fused_key = None, None
         self._plans[key] = st
 
-    def _plan_for(self, uc, triples, c=None, keep=False):
-        """``keep=True``: the plan of the MASKED loop -- one more op, the blend (es_ddim_blend), in front of the step's denoiser ops,
+    def _plan_for(self, uc, triples, c=None, keep=False, sampler=None):
+        """``sampler='plms'``: the plans of the PLMS loop, under a cache key of their own -- 'plan' is the steady iteration (the denoiser
+        ops, then es_plms_update in the place of es_ddim_update) and 'first_plan' iteration 0 (the denoiser ops, es_plms_first_a, the
+        denoiser ops again, es_plms_first_b); the blend of ``keep=True`` sits in front of the FIRST evaluation only (the reference blends
+        once per iteration, before p_sample_plms, plms.py:154-159).  The 'ddim' plans are, op for op, what they have always been.
+        ``keep=True``: the plan of the MASKED loop -- one more op, the blend (es_ddim_blend), in front of the step's denoiser ops,
         and its three inputs: ``x0`` [Ol, C,D,H,W], ``mask`` [Ol], ``knoise`` [S, Ol * latent].  A plan of its own (another cache key):
         without a mask the plan is, op for op, what it has always been."""
         from .parallel import partition
@@ -287,7 +322,9 @@ class ShapeDenoiser:
                                  "no message passing: the cross-attention key [O, 1, context_dim])")
             c = c.reshape(O, -1).to(self.device).float()
         cap = _cap(triples.shape[0])
-        key = (O, cap, 'keep') if keep else (O, cap)
+        sampler = self._sampler_of(sampler)
+        plms = sampler == 'plms'
+        key = ((O, cap, 'keep') if keep else (O, cap)) + (('plms',) if plms else ())
         sig = hash(triples.detach().cpu().numpy().tobytes())
         st = self._plans.get(key)
         if st is None:
@@ -298,7 +335,7 @@ class ShapeDenoiser:
                 z = lambda *sh: torch.zeros(*sh, device=self.device)
                 st = dict(empty=True, x=z(0, *self.z_shape), eps=z(0, *self.z_shape), lo=lo, hi=hi, O=O,
                           codes_local=z(block, 64), codes_all=z(block * self.world, 64), objbuf=None, cdev=None, xc=None)
-                st['sig'] = sig
+                st['sig'], st['sampler'] = sig, sampler
                 self._insert_plan(key, st)
                 return st
             g = GraphIndex(triples, O, self.device, capacity=cap)
@@ -311,6 +348,7 @@ class ShapeDenoiser:
             eps = b.buf(hi - lo, *self.z_shape)
             step = b.buf(1, dtype=torch.int32, zero=True)
             kx0 = kmask = knoise = None
+            n_blend = 1 if keep else 0
             if keep:
                 # the reference blends before p_sample_ddim (samplers/ddim.py:160-163): the denoiser -- conv-pool stem and shape GCN
                 # included -- reads the kept objects' forward-noised latents, so the generated ones are denoised in their context
@@ -323,7 +361,14 @@ class ShapeDenoiser:
                                       gather_rows=block * self.world)
             n_eps_ops = len(b.ops)
             snoise = None
-            if self.ddim_eta != 0.0:
+            plms_ops = None
+            if plms:
+                # the sampler's state: the last three eps, iteration i in slot i % 3, and x at the start of iteration 0
+                ring, xsave = b.buf(3, x.numel(), zero=True), b.buf(x.numel(), zero=True)
+                plms_ops = (b.plms(hip.OP_PLMS_FIRST_A, x, eps, self.coef, step, ring, xsave, push=False),
+                            b.plms(hip.OP_PLMS_FIRST_B, x, eps, self.coef, step, ring, xsave, push=False))
+                b.plms(hip.OP_PLMS, x, eps, self.coef, step, ring, xsave, inc_step=True)
+            elif self.ddim_eta != 0.0:
                 nz = x.numel()
                 snoise = b.buf(self.S, nz)
                 b.update(hip.OP_DDIM, x, eps, self.coef, step, noise=View(snoise, ld=nz), noise_stride=nz, inc_step=True)
@@ -332,7 +377,7 @@ class ShapeDenoiser:
             st = dict(x=x, eps=eps, step=step, snoise=snoise, objbuf=objbuf, ucw=ucd.shape[1], lo=lo, hi=hi, O=O,
                       codes_local=b.codes_local, codes_all=getattr(b, 'codes_all', None), code_cols=b.code_cols,
                       xc=getattr(b, 'xc', None), g=g, pred=getattr(b, 'pred_rows', None), sig=sig,
-                      cdev=getattr(b, 'cdev', None), x0=kx0, mask=kmask, knoise=knoise)
+                      cdev=getattr(b, 'cdev', None), x0=kx0, mask=kmask, knoise=knoise, sampler=sampler)
 
             def sub(ops):
                 b2 = Builder(self.device)
@@ -344,6 +389,15 @@ class ShapeDenoiser:
             if (self.world > 1 or self.force_exchange) and self.w.mp:
                 st['stem_plan'] = sub(b.ops[:b.split])
                 st['main_plan'] = sub(b.ops[b.split:])
+            if plms:
+                fa, fb = plms_ops
+                den = b.ops[n_blend:n_eps_ops]
+                st['first_plan'] = sub(b.ops[:n_eps_ops] + [fa] + den + [fb])
+                if 'stem_plan' in st:
+                    # iteration 0 of the sharded loop: stem -> exchange -> rest + first-a, then once more (no blend) with first-b
+                    st['main_a_plan'] = sub(b.ops[b.split:n_eps_ops] + [fa])
+                    st['stem2_plan'] = sub(b.ops[n_blend:b.split]) if n_blend else st['stem_plan']
+                    st['main_b_plan'] = sub(b.ops[b.split:n_eps_ops] + [fb])
             self._insert_plan(key, st)
         elif st.get('sig') != sig and not st.get('empty'):
             # same size class, another scene graph: rewrite indices / predicate rows in place, keep plans and graphs
@@ -362,10 +416,16 @@ class ShapeDenoiser:
         return st
 
     # -- shard backend protocol of parallel.sharded_ddim_loop ------------------------------------------------
-    def codes_local(self, i):
+    def passes(self, i):
+        """(stem -> exchange -> rest) passes of loop iteration i: 2 in iteration 0 of a PLMS loop (its second evaluation), else 1"""
+        return 2 if (self._cur.get('sampler') == 'plms' and int(i) == 0) else 1
+
+    def codes_local(self, i, p=0):
         st = self._cur
         if not st.get('empty'):
-            st['stem_plan'].sample(st['step'], int(i), 1, use_graph=self._use_graph)     # captured like the main part
+            # pass 1 (PLMS iteration 0): the stem without the blend, at the step counter first-a left (1: the reference's t_next)
+            plan, first = (st['stem2_plan'], 1) if p else (st['stem_plan'], int(i))
+            plan.sample(st['step'], first, 1, use_graph=self._use_graph)     # captured like the main part
         return st['codes_local']
 
     def gather_buffers(self):
@@ -374,13 +434,16 @@ class ShapeDenoiser:
         st = self._cur
         return st['codes_local'], st['codes_all']
 
-    def step(self, i, codes_all):
+    def step(self, i, codes_all, p=0):
         st = self._cur
         if st.get('empty'):
             return
         if codes_all.data_ptr() != st['codes_all'].data_ptr():      # single-process emulations hand in their own tensor
             st['codes_all'][:codes_all.shape[0]].copy_(codes_all)
-        st['main_plan'].sample(st['step'], int(i), 1, use_graph=self._use_graph)
+        plan, first = st['main_plan'], int(i)
+        if st.get('sampler') == 'plms' and int(i) == 0:
+            plan, first = (st['main_b_plan'], 1) if p else (st['main_a_plan'], 0)
+        plan.sample(st['step'], first, 1, use_graph=self._use_graph)
 
     def latents_local(self):
         return self._cur['x']
@@ -389,6 +452,8 @@ class ShapeDenoiser:
         """The DDIM loop of this scene (single GPU) as a model file for hosts without Python (es_model_load + es_shape_sample).
         ``keep=True``: the masked loop; the host fills the regions "x0" [O,C,D,H,W], "mask" [O] and "keep_noise" [S, O x latent]."""
         from .plan import save_model
+        if self.sampler == 'plms':
+            raise NotImplementedError("model files hold the DDIM loop only (es_shape_sample); sampler='plms' has no C host yet")
         assert self.world == 1 and not self.force_exchange
         st = self._plan_for(uc, triples, c, keep=keep)
         regions = dict(x=st['x'], step=st['step'], coef=self.coef)
@@ -415,6 +480,8 @@ class ShapeDenoiser:
         one eager all-gather per step; that matches its peers' captured ones call for call.
         Returns the graph, or None (three-call step)."""
         st = self._cur
+        if st.get('sampler') == 'plms':
+            return None                          # the captured step graph is the DDIM step; PLMS runs the three-call step
         if not self._use_graph or ('stem_plan' not in st and not st.get('empty')) or os.environ.get('ES_STEP_GRAPH', '0') != '1':
             return None
         if 'step_graph' in st:
@@ -461,6 +528,17 @@ class ShapeDenoiser:
         st['eps_plan'].sample(st['step'], int(iteration), 1, use_graph=False)
         return st['eps'].clone()
 
+    @staticmethod
+    def _run_loop(st, n_steps, use_graph):
+        """the unsharded loop of a plan state: DDIM replays 'plan'; PLMS runs iteration 0 ('first_plan': two evaluations, the step
+        counter ends at 1) and replays the steady 'plan' for the others"""
+        if st['sampler'] == 'plms':
+            if n_steps > 0:
+                st['first_plan'].sample(st['step'], 0, 1, use_graph=use_graph)
+                st['plan'].sample(st['step'], 1, n_steps - 1, use_graph=use_graph)
+        else:
+            st['plan'].sample(st['step'], 0, n_steps, use_graph=use_graph)
+
     def _fill_keep(self, st, x0, mask, keep_noise):
         """inputs of the masked loop into the plan's buffers (this rank's objects lo:hi of the scene's)"""
         O, lo, hi = st['O'], st['lo'], st['hi']
@@ -493,7 +571,7 @@ class ShapeDenoiser:
             st['knoise'].copy_(kn.reshape(self.S, -1))
 
     def sample(self, uc, triples, noise1=None, n_steps=None, use_graph=True, c=None, step_noise=None, x0=None, mask=None,
-               keep_noise=None):
+               keep_noise=None, sampler=None):
         """DDIM loop; ``noise1`` f32[1,C,D,H,W] is shared by all objects as in the reference
         (echo2shape.py:507-510); None draws it on the device (world > 1: pass it, or every rank draws its own).
         ``step_noise`` (ddim_eta != 0 only) f32[S, O, C,D,H,W]: the per-step draws of p_sample_ddim, one per OBJECT (noise_like without
@@ -505,13 +583,16 @@ class ShapeDenoiser:
         device).  Before every step the kept rows are set to ``sqrt_ac[t] * x0 + sqrt(1 - ac)[t] * keep_noise[step]``; they take part
         in the step's echo message passing like every other node.  The reference accepts any tensor as mask; this one is per object,
         which is what editing a scene needs.  ``mask=None``: the loop and its plan are what they are without this feature.
+        ``sampler``: 'ddim' / 'plms' for this call (None: the denoiser's own).  PLMS: ``n_steps`` counts ITERATIONS -- iteration 0
+        evaluates the denoiser twice (improved Euler), so k iterations are k + 1 evaluations; the masked loop blends once per iteration,
+        before its first evaluation.
         Returns the latents of ALL objects [O,C,D,H,W] (all-gathered when sharded)."""
         from .parallel import sharded_ddim_loop
         if (mask is None) != (x0 is None):
             raise ValueError('masked DDIM needs both x0 and mask')
         if mask is None and keep_noise is not None:
             raise ValueError('keep_noise without a mask')
-        st = self._plan_for(uc, triples, c, keep=mask is not None)
+        st = self._plan_for(uc, triples, c, keep=mask is not None, sampler=sampler)
         if mask is not None:
             self._fill_keep(st, x0, mask, keep_noise)
         n_steps = self.S if n_steps is None else n_steps
@@ -546,7 +627,7 @@ class ShapeDenoiser:
             self._cur, self._use_graph = st, use_graph
             return loop(self, st['O'], n_steps, self.world, self.group).clone()
         if (self.world == 1 and not self.force_exchange) or not self.w.mp:
-            st['plan'].sample(st['step'], 0, n_steps, use_graph=use_graph)
+            self._run_loop(st, n_steps, use_graph)
             if self.world == 1:
                 return st['x'].clone()
             from .parallel import all_gather_rows         # no message passing: ranks only meet at the end
@@ -573,7 +654,7 @@ def keep_selection(keep_nodes, n_objects):
 
 
 def sample_layout_and_shape(lay, shp, obj_embed, triples, uc, c=None, layout_noise=None, shape_noise=None, use_graph=True,
-                            x0=None, mask=None, keep_noise=None, box_x0=None, box_mask=None, box_keep_noise=None):
+                            x0=None, mask=None, keep_noise=None, box_x0=None, box_mask=None, box_keep_noise=None, shape_sampler=None):
     """Both sampling loops of one scene (EchoScene.py:402-419 runs them back to back) as ONE replayed hipGraph: every replay = one
     DDIM shape step on the main branch and ``T_layout // S_shape`` (= 10) ancestral layout steps on a parallel branch
     (plan.combine_plans), so the latency-bound layout chain -- 131 launches of 32 workgroups per step -- runs inside the gaps
@@ -581,7 +662,9 @@ def sample_layout_and_shape(lay, shp, obj_embed, triples, uc, c=None, layout_noi
     step disappears).  Left-over layout steps (T not a multiple of S) run afterwards.  Returns (boxes x_0 [O, 8], latents z_0).
     ``x0`` / ``mask`` / ``keep_noise``: the masked shape loop (ShapeDenoiser.sample).  ``box_x0`` / ``box_mask`` / ``box_keep_noise``:
     the masked layout loop (LayoutDenoiser.sample) -- its keep plan is then the side branch of the fused graph and runs the left-over
-    steps; the two families are independent of each other."""
+    steps; the two families are independent of each other.
+    ``shape_sampler``: 'ddim' / 'plms' for the shape loop (None: the denoiser's own).  PLMS: iteration 0 (two evaluations) runs unfused,
+    iterations 1..S-1 replay the fused graph, and the layout steps not covered run afterwards."""
     from .plan import combine_plans
     if (box_mask is None) != (box_x0 is None):
         raise ValueError('the masked layout loop needs both box_x0 and box_mask')
@@ -590,7 +673,8 @@ def sample_layout_and_shape(lay, shp, obj_embed, triples, uc, c=None, layout_noi
     if shp.world != 1:
         return lay.sample(obj_embed, triples, noise=layout_noise, use_graph=use_graph, x0=box_x0, mask=box_mask,
                           keep_noise=box_keep_noise), \
-            shp.sample(uc, triples, noise1=shape_noise, c=c, use_graph=use_graph, x0=x0, mask=mask, keep_noise=keep_noise)
+            shp.sample(uc, triples, noise1=shape_noise, c=c, use_graph=use_graph, x0=x0, mask=mask, keep_noise=keep_noise,
+                       sampler=shape_sampler)
     st = lay._plan_for(obj_embed, triples, keep=box_mask is not None)
     if box_mask is not None:
         lay._fill_keep(st, box_x0, box_mask, box_keep_noise)
@@ -601,7 +685,8 @@ def sample_layout_and_shape(lay, shp, obj_embed, triples, uc, c=None, layout_noi
     st['x'].copy_(st['noise'][0])
     if box_mask is not None:
         lay._prime_keep(st)
-    ss = shp._plan_for(uc, triples, c, keep=mask is not None)
+    ss = shp._plan_for(uc, triples, c, keep=mask is not None, sampler=shape_sampler)
+    plms = ss['sampler'] == 'plms'
     if mask is not None:
         shp._fill_keep(ss, x0, mask, keep_noise)
     if shape_noise is None:
@@ -611,13 +696,17 @@ def sample_layout_and_shape(lay, shp, obj_embed, triples, uc, c=None, layout_noi
     done = 0
     if r >= 1 and use_graph:
         key = (id(st['plan']), id(ss['plan']), r)
+        # (one fused graph per shape denoiser: a caller that alternates ``shape_sampler`` per call on ONE denoiser re-captures it every
+        #  call; the scene layer keeps a denoiser per sampler, so each has its own)
         if getattr(shp, '_fused_key', None) != key:
             shp._fused, shp._fused_key = combine_plans(shp.device, ss['plan'], st['plan'], side_repeat=r), key
         st['step'].zero_()
-        shp._fused.sample(ss['step'], 0, shp.S, use_graph=True)
-        done = r * shp.S
+        if plms:
+            ss['first_plan'].sample(ss['step'], 0, 1, use_graph=True)
+        shp._fused.sample(ss['step'], 1 if plms else 0, shp.S - (1 if plms else 0), use_graph=True)
+        done = r * (shp.S - (1 if plms else 0))
     else:
-        ss['plan'].sample(ss['step'], 0, shp.S, use_graph=use_graph)
+        shp._run_loop(ss, shp.S, use_graph)
     if done < lay.T:
         st['plan'].sample(st['step'], done, lay.T - done, use_graph=use_graph)
     return st['x'].clone(), ss['x'].clone()

@@ -140,3 +140,24 @@ class ShapeSchedule:
         self.sqrt_one_minus_alphas_cumprod = torch.tensor(np.sqrt(1.0 - ac64), dtype=torch.float32)
         tsi = torch.from_numpy(self.timesteps.copy())
         self.keep_tab = torch.stack([self.sqrt_alphas_cumprod[tsi], self.sqrt_one_minus_alphas_cumprod[tsi]], dim=1).contiguous()   # [S, 2] by iteration
+
+
+SHAPE_SAMPLERS = ('ddim', 'plms')
+
+
+def plms_evaluations(n_timesteps, n_steps=None):
+    """The denoiser evaluations of a PLMS run (PLMSSampler.plms_sampling / p_sample_plms, samplers/plms.py:149-247) over a schedule of
+    ``n_timesteps`` timesteps, in order, as (table row, kind): the row of the per-iteration tables (ShapeSchedule.timesteps, the
+    time-embedding table) the evaluation reads, and what consumes its eps --
+        'first'   iteration 0, first evaluation (row 0): improved Euler's predictor (es_plms_first_a); its eps enters the history;
+        'second'  iteration 0, second evaluation at the NEXT timestep (row 1, the reference's t_next): the corrector (es_plms_first_b);
+        'steady'  iteration i >= 1 (row i): Adams-Bashforth on the eps of the last min(i, 3) iterations (es_plms_update).
+    ``n_steps`` iterations (None: all) make n_steps + 1 evaluations."""
+    n = int(n_timesteps) if n_steps is None else int(n_steps)
+    if n_timesteps < 2:
+        raise ValueError('PLMS needs at least 2 timesteps')
+    if n < 0 or n > n_timesteps:
+        raise ValueError('n_steps must be in [0, %d]' % n_timesteps)
+    if n == 0:
+        return []
+    return [(0, 'first'), (1, 'second')] + [(i, 'steady') for i in range(1, n)]

@@ -231,6 +231,36 @@ typedef struct es_blend_args {
     int32_t O, n;           /* objects, floats per object (n % 4 == 0)                          */
 } es_blend_args;
 int es_ddim_blend(const es_blend_args* args, es_stream stream);
+/* PLMS sampling of the shape branch (PLMSSampler, diffusion_shape/samplers/plms.py:149-247): pseudo linear multistep on the DDIM schedule,
+ * S + 1 denoiser evaluations for S iterations.  coef is the table of es_ddim_update (eta = 0).  ring [3][ring_stride] fp32 holds the eps of
+ * the last three iterations, iteration i in slot i % 3; with e = the slab sum of eps (fixed order, as es_ddim_update) and
+ * ddim(x, e, c) = c[2] * ((x - c[0] * e) / c[1]) + c[3] * e:
+ *   es_plms_first_a (iteration 0, after the first evaluation):  xsave = x; ring[0] = e; x = ddim(x, e, coef row 0); *step = 1
+ *       -- the second evaluation then reads time-embedding row 1, the reference's t_next;
+ *   es_plms_first_b (iteration 0, after the second evaluation): x = ddim(xsave, (ring[0] + e) / 2, coef row 0); *step is not touched;
+ *   es_plms_update  (iteration st = *step >= 1), h1, h2, h3 = ring[(st-1) % 3], ring[(st-2) % 3], ring[(st-3) % 3]:
+ *       st == 1: e' = (3 e - h1) / 2;  st == 2: e' = (23 e - 16 h1 + 5 h2) / 12;  st >= 3: e' = (55 e - 59 h1 + 37 h2 - 9 h3) / 24
+ *       x = ddim(x, e', coef row st); ring[st % 3] = e (not e'); *step = st + 1 when inc_step != 0.
+ * No fp contraction, the reference's expression order.  n % 4 == 0, ring_stride % 4 == 0 (and eps_slab_stride when eps_nslab > 1); x, eps,
+ * ring and xsave 16-byte aligned and disjoint.  xsave is used by the two first-iteration calls only (es_plms_update: may be NULL).
+ * Two conditions are the CALLER's and are not checked: the buffers do not overlap, and coef holds a row for every value the step
+ * counter takes (es_plms_args carries no table length, as es_update_args does not). */
+typedef struct es_plms_args {
+    float* x;               /* [n] state, updated in place                                      */
+    const float* eps;       /* [n] network output (slab tensor as in es_update_args)            */
+    int32_t eps_nslab, eps_slab_stride;
+    const float* coef;      /* [n_steps][coef_stride] (es_ddim_update's four numbers per step)  */
+    int32_t coef_stride;
+    int32_t n;
+    int32_t* step;
+    int32_t inc_step;       /* es_plms_update only                                              */
+    int32_t ring_stride;    /* floats between the ring's slots (>= n)                           */
+    float* ring;            /* [3][ring_stride]                                                 */
+    float* xsave;           /* [n]                                                              */
+} es_plms_args;
+int es_plms_update(const es_plms_args* args, es_stream stream);
+int es_plms_first_a(const es_plms_args* args, es_stream stream);
+int es_plms_first_b(const es_plms_args* args, es_stream stream);
 /* Masked ancestral loop of the layout branch (keep given boxes while the other nodes are placed around them).  The reference's layout
  * GaussianDiffusion has no masked loop; the definition is the one its shape sampler uses (DDIMSampler.ddim_sampling, samplers/ddim.py:
  * 160-163) carried over to p_sample_loop_sg (diffusion_ddpm.py:330-345) with GaussianDiffusion.q_sample (:191-201): before the denoiser
@@ -492,8 +522,10 @@ enum {
     ES_OP_CONV_F32 = 16, ES_OP_ATTN_F32 = 17,     /* the fp32-operand validation route: es_conv_f32 / es_attention_f32 on the same argument structs */
     ES_OP_DDIM_BLEND = 18,                        /* es_ddim_blend (es_blend_args): the masked-DDIM blend in front of a step's denoiser */
     ES_OP_CONV_C1 = 19,                           /* es_conv_c1_f32 (es_conv_c1_args): the VQ-VAE encoder's one-channel conv_in */
-    ES_OP_DDPM_KEEP = 21                          /* es_ddpm_update_keep (es_ddpm_keep_args): the layout update that also carries the kept rows.
+    ES_OP_DDPM_KEEP = 21,                         /* es_ddpm_update_keep (es_ddpm_keep_args): the layout update that also carries the kept rows.
                                                      (20 stays unassigned: es_op_pointer_offsets(20) is pinned to "unknown kind") */
+    ES_OP_PLMS = 23, ES_OP_PLMS_FIRST_A = 24, ES_OP_PLMS_FIRST_B = 25    /* es_plms_update / es_plms_first_a / es_plms_first_b (es_plms_args);
+                                                     22 stays unassigned, as 20: es_op_pointer_offsets(22) is pinned to "unknown kind" */
 };
 /* Row select: out[r, 0..n) = table[*step, 0..n) for r < rows.  The timestep-dependent but node-independent products of a
  * denoiser (time MLP, all ResBlock emb projections, box/shape time embedding) are tabulated once per schedule
@@ -519,7 +551,7 @@ typedef struct es_op {
         es_linear_args linear; es_update_args update; es_copy_args copy; es_conv_args conv;
         es_gn_args gn; es_ln_args ln; es_attn_args attn; es_geglu_args geglu; es_tocl_args tocl;
         es_stem_args stem; es_vq_args vq; es_rowsel_args rowsel; es_blend_args blend; es_conv_c1_args conv_c1;
-        es_ddpm_keep_args keep;
+        es_ddpm_keep_args keep; es_plms_args plms;
     } u;
 } es_op;
 
