@@ -31,6 +31,9 @@ def _dev(module):
     return torch.device('cpu')
 
 
+_BOX_OPTS = ('keep_box_nodes', 'keep_boxes', 'keep_box_noise')
+
+
 def _hip_device(d):
     if d.type != 'cuda':
         raise RuntimeError('the sampling path runs on the MI355X HIP library only: move the model to the GPU '
@@ -92,12 +95,14 @@ class EchoToLayout(nn.Module):
         ``clip_denoised`` reaches the loop (gen_samples_sg, echo2layout.py:108; diffusion_ddpm.py:243-244).  ``ret_traj``, ``ddim``,
         ``text`` and ``batch_seeds`` are accepted and -- exactly as in the reference, whose ``sample`` (echo2layout.py:102-110)
         passes none of them on -- have no effect.  ``x0`` / ``mask`` / ``keep_noise``: the masked loop (LayoutDenoiser.sample)."""
-        samples = self._denoiser().sample(self.uc_rel, self.preds, noise=noise, clip_denoised=bool(clip_denoised),
-                                          x0=x0, mask=mask, keep_noise=keep_noise)
+        return self.split_boxes(self._denoiser().sample(self.uc_rel, self.preds, noise=noise, clip_denoised=bool(clip_denoised),
+                                                        x0=x0, mask=mask, keep_noise=keep_noise))
+
+    def split_boxes(self, x):
+        """loop state [O, bbox_dim] -> its sizes | translations | angles columns"""
         s, t = self.size_dim, self.translation_dim
-        return {'sizes': samples[:, 0:s].contiguous(),
-                'translations': samples[:, s:s + t].contiguous(),
-                'angles': samples[:, s + t:self.bbox_dim].contiguous()}
+        return {'sizes': x[:, 0:s].contiguous(), 'translations': x[:, s:s + t].contiguous(),
+                'angles': x[:, s + t:self.bbox_dim].contiguous()}
 
 
 class EchoToShape(object):
@@ -404,12 +409,32 @@ class _SceneModel(nn.Module):
             x0[rows] = boxes[src].to(device).float()
         return dict(x0=x0, mask=mask.to(device), keep_noise=keep_box_noise)
 
-    def _layout(self, triples, obj_embed_, relation_cond, noise=None, keep_box_nodes=None, keep_boxes=None, keep_box_noise=None):
+    def _layout(self, triples, obj_embed_, relation_cond, noise=None, *, keep_box_nodes=None, keep_boxes=None, keep_box_noise=None):
         kw = self._box_keep(keep_box_nodes, keep_boxes, keep_box_noise, obj_embed_.shape[0], obj_embed_.device)
         self.LayoutDiff.set_input({'preds': triples, 'box': None, 'uc_b': obj_embed_, 'c_b': relation_cond,
                                    'obj_id_to_scene': None})
         return self.LayoutDiff.generate_layout_sg(box_dim=self.diff_cfg.layout_branch.denoiser_kwargs.in_channels,
                                                   noise=noise, **kw)
+
+    def _splice(self, latent, latent_m, rows, strict=False):
+        """the manipulator's rows for the touched nodes ``rows``, the original ones for the others (EchoScene.py:440-448) -- or the
+        manipulator's for all of them (``replace_all_latent``).  Entries outside the node list are ignored (``manipulated_nodes``) or,
+        ``strict`` (added nodes), indexed as they are: an IndexError tells the caller about a wrong ``missing_nodes``"""
+        if self.replace_all_latent:
+            return latent_m
+        latent = latent.clone()
+        for t in sorted(rows):
+            if strict or 0 <= int(t) < latent.shape[0]:
+                latent[t] = latent_m[t]
+        return latent
+
+    @staticmethod
+    def _keep_vector(n, rows, device=None):
+        """1 for an untouched node, 0 for one of ``rows``: f32 [n, 1] on ``device`` (EchoScene.py, EchoLayout.py:342-348), or -- no
+        device -- the plain list only EchoLayout's _with_additions variant returns"""
+        hit = {int(t) for t in rows}
+        flags = [0 if i in hit else 1 for i in range(n)]
+        return flags if device is None else torch.tensor(flags, dtype=torch.float32, device=device).reshape(n, 1)
 
 
 class Sg2ScDiffModel(_SceneModel):
@@ -451,15 +476,7 @@ class Sg2ScDiffModel(_SceneModel):
         torch.cuda.synchronize()
         return o.t.unsqueeze(1)
 
-    def _shapes(self, gen_shape, dec_objs, dec_triples, obj_embed_, latent, shape_noise=None, shape_sampler=None, shape_steps=None):
-        if not gen_shape:
-            return None
-        uc = self._rel_s(obj_embed_)
-        c = self._rel_s(latent)
-        return self.ShapeDiff.rel2shape({'obj_cat': dec_objs, 'triples': dec_triples, 'c_s': c, 'uc_s': uc},
-                                        noise=shape_noise, shape_sampler=shape_sampler, shape_steps=shape_steps)
-
-    def _layout_and_shapes(self, gen_shape, dec_objs, dec_triples, obj_embed_, latent, layout_noise, shape_noise,
+    def _layout_and_shapes(self, gen_shape, dec_objs, dec_triples, obj_embed_, latent, layout_noise, shape_noise, *,
                            keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None, keep_boxes=None,
                            keep_box_noise=None, shape_sampler=None, shape_steps=None):
         """The two loops only share the setup (the reference runs them back to back, EchoScene.py:402-419).  Here they are
@@ -482,7 +499,7 @@ class Sg2ScDiffModel(_SceneModel):
         if not gen_shape:
             if keep_nodes is not None:
                 raise ValueError('keep_nodes / keep_sdfs keep SHAPES: they need gen_shape=True')
-            return None, self._layout(dec_triples, obj_embed_, latent, layout_noise, keep_box_nodes, keep_boxes, keep_box_noise)
+            return None, self._layout(dec_triples, obj_embed_, latent, layout_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise)
         bk = self._box_keep(keep_box_nodes, keep_boxes, keep_box_noise, obj_embed_.shape[0], obj_embed_.device)
         from ..samplers import sample_layout_and_shape
         uc = self._rel_s(obj_embed_)
@@ -496,17 +513,15 @@ class Sg2ScDiffModel(_SceneModel):
         if shape_noise is None:       # the reference seeds this draw from the wall clock (echo2shape.py:502)
             g = torch.Generator(device=sden.device).manual_seed(int(time.time()))
             shape_noise = torch.randn((1,) + tuple(S.z_shape), device=sden.device, generator=g)
-        kw, rows, kept = {}, [], None
+        kw, rows, kept = dict(shape_sampler=sden.sampler), [], None      # (the sampler ``sden`` was chosen by)
         if keep_nodes is not None:
             x0, mask, rows, kept = S.keep_inputs(keep_nodes, keep_sdfs, uc.shape[0], sden.device)
-            kw = dict(x0=x0, mask=mask, keep_noise=keep_noise)
+            kw.update(x0=x0, mask=mask, keep_noise=keep_noise)
         if bk:
             kw.update(box_x0=bk['x0'], box_mask=bk['mask'], box_keep_noise=bk['keep_noise'])
         x, z = sample_layout_and_shape(L._denoiser(), sden, obj_embed_, dec_triples, uc, c if need_c else None,
                                        layout_noise=layout_noise, shape_noise=shape_noise, **kw)
-        s_, t_ = L.size_dim, L.translation_dim
-        boxes = {'sizes': x[:, 0:s_].contiguous(), 'translations': x[:, s_:s_ + t_].contiguous(),
-                 'angles': x[:, s_ + t_:L.bbox_dim].contiguous()}
+        boxes = L.split_boxes(x)
         S.gen_z = z
         if rows:
             # decode only the generated nodes; the kept rows are the caller's SDFs, bit for bit
@@ -533,64 +548,43 @@ class Sg2ScDiffModel(_SceneModel):
         oe, _, latent_m = self._setup(dec_objs, dec_triplets, dec_text_feat, dec_rel_feat,
                                       dec_objs, dec_triplets, dec_text_feat, dec_rel_feat)
         sdf, boxes = self._layout_and_shapes(gen_shape, dec_objs, dec_triplets, oe, latent_m, layout_noise, shape_noise,
-                                             keep_nodes, keep_sdfs, keep_noise, keep_box_nodes, keep_boxes, keep_box_noise,
-                                             shape_sampler, shape_steps)
+                                             keep_nodes=keep_nodes, keep_sdfs=keep_sdfs, keep_noise=keep_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise,
+                                             shape_sampler=shape_sampler, shape_steps=shape_steps)
         return {'shapes': sdf}, boxes
 
-    def _edited(self, enc, dec, touched, added, gen_shape, layout_noise, shape_noise, keep_nodes=None, keep_sdfs=None,
-                keep_noise=None, keep_box_nodes=None, keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None):
-        oe, latent, latent_m = self._setup(*enc, *dec, change_rows=touched, added_rows=added)
-        if not self.replace_all_latent:
-            latent = latent.clone()
-            for t in sorted(touched):                       # take original nodes when untouched (:440-448)
-                if 0 <= int(t) < latent.shape[0]:
-                    latent[t] = latent_m[t]
-        else:
-            latent = latent_m
-        sdf, boxes = self._layout_and_shapes(gen_shape, dec[0], dec[1], oe, latent, layout_noise, shape_noise,
-                                             keep_nodes, keep_sdfs, keep_noise, keep_box_nodes, keep_boxes, keep_box_noise,
-                                             shape_sampler, shape_steps)
-        keep = torch.ones(len(boxes['translations']), 1, device=oe.device)
-        for t in touched:
-            if 0 <= int(t) < keep.shape[0]:
-                keep[int(t)] = 0
-        return keep, {'shapes': sdf}, boxes
+    def _edited(self, enc, dec, touched, added, gen_shape, layout_noise, shape_noise, change_rows=None, strict=False, **opts):
+        """the two editing calls: ``touched`` nodes take the manipulator's latent rows and are 0 in the returned keep vector, ``added``
+        rows are inserted as zeros, ``change_rows`` (default: ``touched``) get the change noise; ``opts``: the options, by keyword"""
+        oe, latent, latent_m = self._setup(*enc, *dec, change_rows=touched if change_rows is None else change_rows, added_rows=added)
+        sdf, boxes = self._layout_and_shapes(gen_shape, dec[0], dec[1], oe, self._splice(latent, latent_m, touched, strict),
+                                             layout_noise, shape_noise, **opts)
+        return self._keep_vector(len(boxes['translations']), touched, oe.device), {'shapes': sdf}, boxes
 
     @torch.no_grad()
     def sample_with_changes(self, enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triplets,
                             dec_text_feat, dec_rel_feat, manipulated_nodes, gen_shape=False, layout_noise=None,
                             shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None,
-               keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None):
+                            keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None):
         """EchoScene.py:422-472.  ``keep_nodes`` / ``keep_sdfs`` (keyword-only): see _layout_and_shapes."""
         return self._edited((enc_objs, enc_triples, enc_text_feat, enc_rel_feat),
                             (dec_objs, dec_triplets, dec_text_feat, dec_rel_feat),
-                            list(manipulated_nodes), [], gen_shape, layout_noise, shape_noise, keep_nodes, keep_sdfs, keep_noise,
-                            keep_box_nodes, keep_boxes, keep_box_noise, shape_sampler, shape_steps)
+                            list(manipulated_nodes), [], gen_shape, layout_noise, shape_noise,
+                            keep_nodes=keep_nodes, keep_sdfs=keep_sdfs, keep_noise=keep_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise,
+                            shape_sampler=shape_sampler, shape_steps=shape_steps)
 
     @torch.no_grad()
     def sample_with_additions(self, enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triplets,
                               dec_text_feat, dec_rel_feat, missing_nodes, gen_shape=False, layout_noise=None,
                               shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None,
-               keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None):
+                              keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None):
         """EchoScene.py:474-532: zero rows inserted at ``missing_nodes[i] + i``; note the reference draws the
         change noise for rows listed in ``missing_nodes`` (:489-494) but splices / masks ``nodes_added``."""
         added = [m + i for i, m in enumerate(missing_nodes)]
-        oe, latent, latent_m = self._setup(enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triplets,
-                                           dec_text_feat, dec_rel_feat, change_rows=list(missing_nodes),
-                                           added_rows=added)
-        if not self.replace_all_latent:
-            latent = latent.clone()
-            for t in sorted(added):
-                latent[t] = latent_m[t]
-        else:
-            latent = latent_m
-        sdf, boxes = self._layout_and_shapes(gen_shape, dec_objs, dec_triplets, oe, latent, layout_noise, shape_noise,
-                                             keep_nodes, keep_sdfs, keep_noise, keep_box_nodes, keep_boxes, keep_box_noise,
-                                             shape_sampler, shape_steps)
-        keep = torch.ones(len(boxes['translations']), 1, device=oe.device)
-        for t in added:
-            keep[t] = 0
-        return keep, {'shapes': sdf}, boxes
+        return self._edited((enc_objs, enc_triples, enc_text_feat, enc_rel_feat),
+                            (dec_objs, dec_triplets, dec_text_feat, dec_rel_feat),
+                            added, added, gen_shape, layout_noise, shape_noise, change_rows=list(missing_nodes), strict=True,
+                            keep_nodes=keep_nodes, keep_sdfs=keep_sdfs, keep_noise=keep_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise,
+                            shape_sampler=shape_sampler, shape_steps=shape_steps)
 
     def state_dict(self, epoch=None, counter=None, **kw):
         """EchoScene.py:534-543 when called with (epoch, counter); plain nn.Module.state_dict otherwise."""
@@ -619,48 +613,30 @@ class Sg2BoxDiffModel(_SceneModel):
         oe, _, latent_m = self._setup(dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat,
                                       dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat,
                                       manip_pred_table='pred_embeddings_man_dc')
-        return self._layout(dec_triplets, oe, latent_m, layout_noise, keep_box_nodes, keep_boxes, keep_box_noise)
+        return self._layout(dec_triplets, oe, latent_m, layout_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise)
+
+    def _edited(self, enc, dec, touched, added, layout_noise, keep_list=False, **box_opts):     # (keep_list: the additions call)
+        """the two editing calls: the ``touched`` nodes get the change noise (sic for additions: nodes_added here, EchoLayout.py:367-372;
+        EchoScene draws it for missing_nodes), take the manipulator's latent rows and are 0 in the returned keep vector"""
+        oe, latent, latent_m = self._setup(*enc, *dec, change_rows=touched, added_rows=added, manip_pred_table='pred_embeddings_man_dc')
+        boxes = self._layout(dec[1], oe, self._splice(latent, latent_m, touched, strict=keep_list), layout_noise, **box_opts)
+        return self._keep_vector(len(boxes['translations']), touched, None if keep_list else oe.device), boxes
 
     @torch.no_grad()
     def sampleBoxes_with_changes(self, enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triples,
                                  dec_text_feat, dec_rel_feat, manipulated_nodes, layout_noise=None, *, keep_box_nodes=None,
                                  keep_boxes=None, keep_box_noise=None):
-        touched = list(manipulated_nodes)
-        oe, latent, latent_m = self._setup(enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triples,
-                                           dec_text_feat, dec_rel_feat, change_rows=touched,
-                                           manip_pred_table='pred_embeddings_man_dc')
-        if not self.replace_all_latent:
-            latent = latent.clone()
-            for t in sorted(touched):
-                if 0 <= int(t) < latent.shape[0]:
-                    latent[t] = latent_m[t]
-        else:
-            latent = latent_m
-        boxes = self._layout(dec_triples, oe, latent, layout_noise, keep_box_nodes, keep_boxes, keep_box_noise)
-        # f32 [O,1] tensor on the model's device (EchoLayout.py:342-348); only the _with_additions variant returns a list
-        keep = torch.ones(len(boxes['translations']), 1, device=oe.device)
-        for t in touched:
-            if 0 <= int(t) < keep.shape[0]:
-                keep[int(t)] = 0
-        return keep, boxes
+        # keep: f32 [O,1] tensor on the model's device (EchoLayout.py:342-348); only the _with_additions variant returns a list
+        return self._edited((enc_objs, enc_triples, enc_text_feat, enc_rel_feat), (dec_objs, dec_triples, dec_text_feat, dec_rel_feat),
+                            list(manipulated_nodes), [], layout_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise)
 
     @torch.no_grad()
     def sampleBoxes_with_additions(self, enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triples,
                                    dec_text_feat, dec_rel_feat, missing_nodes, layout_noise=None, *, keep_box_nodes=None,
                                    keep_boxes=None, keep_box_noise=None):
         added = [m + i for i, m in enumerate(missing_nodes)]
-        oe, latent, latent_m = self._setup(enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triples,
-                                           dec_text_feat, dec_rel_feat, change_rows=added,   # sic: nodes_added here,
-                                           added_rows=added, manip_pred_table='pred_embeddings_man_dc')   # EchoLayout.py:367-372
-        if not self.replace_all_latent:
-            latent = latent.clone()
-            for t in sorted(added):
-                latent[t] = latent_m[t]
-        else:
-            latent = latent_m
-        boxes = self._layout(dec_triples, oe, latent, layout_noise, keep_box_nodes, keep_boxes, keep_box_noise)
-        keep = [0 if i in added else 1 for i in range(len(boxes['translations']))]
-        return keep, boxes
+        return self._edited((enc_objs, enc_triples, enc_text_feat, enc_rel_feat), (dec_objs, dec_triples, dec_text_feat, dec_rel_feat),
+                            added, added, layout_noise, keep_list=True, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise)
 
     def state_dict(self, epoch=None, counter=None, **kw):
         sd = super().state_dict(**kw)
@@ -735,7 +711,7 @@ class SGDiff(nn.Module):
 
     @staticmethod
     def _box_kw(kw):
-        return {k: kw.get(k) for k in ('keep_box_nodes', 'keep_boxes', 'keep_box_noise')}
+        return {k: kw.get(k) for k in _BOX_OPTS}
 
     def sample_box_and_shape(self, dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat, gen_shape=False,
                              **noise):

@@ -677,6 +677,15 @@ class Plan:
             pass
 
 
+def sub_plan(parent, ops):
+    """A plan of ``ops`` -- a slice or a recombination of the op list of ``parent`` (a Builder or a Plan) -- on the parent's buffers: it
+    shares ``keep`` and ``tags`` and reports the parent's ``weight_bytes`` / ``flops``; it allocates nothing and claims no scratch."""
+    b = Builder(getattr(parent, 'device', None))
+    b.ops, b.keep, b.tags = list(ops), parent.keep, parent.tags
+    b.weight_bytes, b.flops = parent.weight_bytes, parent.flops
+    return b.finish()
+
+
 def save_model(plan, path, regions):
     """Serialise ``plan`` and every device allocation it references into a model file that a host WITHOUT Python loads with
     ``es_model_load`` and runs with ``es_layout_sample`` / ``es_shape_sample`` / ``es_vq_decode`` (include/echoscene_hip.h).

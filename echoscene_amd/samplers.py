@@ -1,12 +1,13 @@
 """Loop owners on the host side: thin objects that own packed weights + per-graph plans and call
 the native sampling loop.  They mirror ``EchoToLayout`` / ``EchoToShape`` of the reference
 (model/networks/diffusion_layout/echo2layout.py, diffusion_shape/echo2shape.py)."""
+import math
 import os
 
 import torch
 
 from . import hip
-from .plan import (Builder, GraphIndex, View, GCNWeights, UNet1DWeights, emit_gcn, emit_unet1d_step, time_tables)
+from .plan import (Builder, GraphIndex, View, GCNWeights, UNet1DWeights, emit_gcn, emit_unet1d_step, time_tables, sub_plan)
 from .plan_vol import UNet3DWeights, emit_unet3d_step, VQWeights, emit_vq_decode, VQEncWeights, emit_vq_encode
 from .schedules import LayoutSchedule, ShapeSchedule, timestep_embedding_table, SHAPE_SAMPLERS
 
@@ -47,6 +48,118 @@ def gcn_forward(sd, prefix, obj, pred, triples, device=None, weights=None, pooli
     return oo.t, out_p
 
 
+# emit / compose / stage: EMIT a loop step's ops on any Builder (no denoiser, no device: the CPU tests plan with the same
+# functions), COMPOSE the op list into a state's named plans, STAGE a call's inputs into the state in a fixed order of the device draws
+SUB_PLANS = ('plan', 'eps_plan', 'stem_plan', 'main_plan', 'first_plan', 'main_a_plan', 'stem2_plan', 'main_b_plan')
+STATE_KEYS = SUB_PLANS + ('x', 'eps', 'step', 'noise', 'snoise', 'x0', 'mask', 'knoise', 'objbuf', 'lo', 'hi', 'O', 'g', 'pred', 'sig',
+                          'sampler', 'codes_local', 'codes_all', 'code_cols', 'xc', 'cdev', 'oe_w', 'ucw')
+
+
+def new_state(**kw):
+    """a plan state with EVERY key present (None where a plan has no such buffer or sub-plan) and ``empty`` False"""
+    st = dict.fromkeys(STATE_KEYS)
+    st['empty'] = False
+    st.update(kw)
+    return st
+
+
+def emit_layout_step(b, w, g, obj_embed, temb, tables, T, coef=None, keep_tab=None, clip=False, keep=False, eps_out=None):
+    """The layout loop step on ``b``: one UNet1D evaluation on x [O, 8] at the iteration ``step`` counts, then -- with the schedule's
+    ``coef`` table -- the ancestral update (``keep``: es_ddpm_update_keep, which also carries the kept rows; it reads ``keep_tab``).
+    ``clip``: clip_denoised of the update.  ``coef=None``: the denoiser alone; ``eps_out``: a plain eps tensor instead of the output
+    conv's K slices.  Buffers are allocated in a fixed order; returns them by name (``n_eps_ops``: the ops in front of the update)."""
+    O, D = g.O, w.in_ch
+    x = b.buf(O, D)
+    step = b.buf(1, dtype=torch.int32, zero=True)
+    noise = b.buf(T + 1, O, D)
+    oe = b.dev(obj_embed)
+    objbuf = emit_unet1d_step(b, w, g, x, oe, temb, step, eps_out, tables=tables)
+    eps = b.tags['eps']                                  # View: the output conv's K slices (the update sums the slabs)
+    out = dict(x=x, step=step, noise=noise, objbuf=objbuf, oe_w=oe.shape[1], eps=eps, n_eps_ops=len(b.ops), pred=b.pred_rows)
+    if coef is None:
+        return out
+    draws = View(noise[1:].reshape(T, O * D), ld=O * D)
+    if keep:
+        out.update(x0=b.buf(O, D, zero=True), mask=b.buf(O, zero=True), knoise=b.buf(T, O * D, zero=True))
+        b.update_keep(x, eps, coef, step, draws, O * D, out['x0'], out['mask'], out['knoise'], keep_tab, inc_step=True, clip_x0=clip)
+    else:
+        b.update(hip.OP_DDPM, x, eps, coef, step, noise=draws, noise_stride=O * D, inc_step=True, clip_x0=clip)
+    return out
+
+
+def emit_shape_step(b, w, g, uc, temb, tables, coef, keep_tab, S, z_shape, lo, hi, c_local=None, gather_rows=None, keep=False,
+                    plms=False, step_noise=False):
+    """The shape loop step on ``b`` for the objects lo:hi of the graph: the blend of the masked loop (``keep``; the reference blends
+    before p_sample_ddim, samplers/ddim.py:160-163: the denoiser -- conv-pool stem and shape GCN included -- reads the kept objects'
+    forward-noised latents), one UNet3D evaluation, then the sampler's tail: es_ddim_update, the same with the per-step draws
+    (``step_noise``: eta != 0), or es_plms_update (``plms``; its two first-iteration ops are returned as ``first_ops``, not appended).
+    Sharding hints travel as attributes of ``b`` (shard_block, force_exchange, o_hint), as the results of emit_unet3d_step do."""
+    x = b.buf(hi - lo, *z_shape)
+    eps = b.buf(hi - lo, *z_shape)
+    step = b.buf(1, dtype=torch.int32, zero=True)
+    out = dict(x=x, eps=eps, step=step, n_blend=1 if keep else 0, first_ops=(None, None))
+    if keep:
+        out.update(x0=b.buf(hi - lo, *z_shape, zero=True), mask=b.buf(hi - lo, zero=True), knoise=b.buf(S, x.numel(), zero=True))
+        b.blend(x, out['x0'], out['mask'], out['knoise'], keep_tab, step)
+    ucd = b.dev(uc)
+    b.xc = b.cdev = b.pred_rows = None                   # (results emit_unet3d_step leaves on the Builder; not every variant has these)
+    out['objbuf'] = emit_unet3d_step(b, w, g, x, ucd, temb, step, eps, dims=z_shape[1:], lo=lo, hi=hi, c_dev=c_local, tables=tables,
+                                     gather_rows=gather_rows)
+    out.update(ucw=ucd.shape[1], n_eps_ops=len(b.ops), split=b.split, codes_local=b.codes_local, codes_all=b.codes_all,
+               code_cols=b.code_cols, xc=b.xc, cdev=b.cdev, pred=b.pred_rows)
+    if plms:
+        # the sampler's state: the last three eps, iteration i in slot i % 3, and x at the start of iteration 0
+        ring, xsave = b.buf(3, x.numel(), zero=True), b.buf(x.numel(), zero=True)
+        out['first_ops'] = (b.plms(hip.OP_PLMS_FIRST_A, x, eps, coef, step, ring, xsave, push=False),
+                            b.plms(hip.OP_PLMS_FIRST_B, x, eps, coef, step, ring, xsave, push=False))
+        b.plms(hip.OP_PLMS, x, eps, coef, step, ring, xsave, inc_step=True)
+    elif step_noise:
+        nz = x.numel()
+        out['snoise'] = b.buf(S, nz)
+        b.update(hip.OP_DDIM, x, eps, coef, step, noise=View(out['snoise'], ld=nz), noise_stride=nz, inc_step=True)
+    else:
+        b.update(hip.OP_DDIM, x, eps, coef, step, inc_step=True)
+    return out
+
+
+def compose_step_plans(ops, n_blend, split, n_eps_ops, first_a, first_b, plms=False, sharded=False):
+    """The op lists of a shape plan state's sub-plans, by name (SUB_PLANS; None: this state has no such plan).  ``ops``: the steady
+    step = ``n_blend`` blend ops, the denoiser (the echo exchange sits in front of op ``split``), one sampler op behind ``n_eps_ops``.
+    ``sharded``: 'stem_plan' + 'main_plan' = the step cut at the exchange.  ``plms``: 'first_plan' is iteration 0 -- the step with
+    ``first_a`` for the sampler op, then the denoiser once more (no blend: the reference blends once per iteration) with ``first_b``;
+    sharded, its two passes are stem -> 'main_a_plan' and 'stem2_plan' (the stem without the blend) -> 'main_b_plan'."""
+    out = dict.fromkeys(SUB_PLANS)
+    out['plan'], out['eps_plan'] = ops, ops[:n_eps_ops]
+    if sharded:
+        out['stem_plan'], out['main_plan'] = ops[:split], ops[split:]
+    if plms:
+        out['first_plan'] = ops[:n_eps_ops] + [first_a] + ops[n_blend:n_eps_ops] + [first_b]
+        if sharded:
+            out['main_a_plan'] = ops[split:n_eps_ops] + [first_a]
+            out['stem2_plan'] = ops[n_blend:split] if n_blend else out['stem_plan']
+            out['main_b_plan'] = ops[split:n_eps_ops] + [first_b]
+    return out
+
+
+def _check_keep_pair(x0, mask, keep_noise, loop, arg=''):
+    """x0 and mask go together, and keep_noise needs them (``arg``: the prefix the caller's keywords carry)"""
+    if (mask is None) != (x0 is None):
+        raise ValueError('%s needs both %sx0 and %smask' % (loop, arg, arg))
+    if mask is None and keep_noise is not None:
+        raise ValueError('%skeep_noise without a %smask' % (arg, arg))
+
+
+def _check_mask(x0, mask, shape, loop, form, unit):
+    """mask [O] of zeros and ones and x0 of ``shape`` = [O, ...] for the masked loop ``loop``; returns (x0, mask f32 [O])"""
+    mask = torch.as_tensor(mask, dtype=torch.float32).reshape(-1)
+    x0 = torch.as_tensor(x0)
+    if mask.numel() != shape[0] or tuple(x0.shape) != tuple(shape):
+        raise ValueError('%s: x0 must be %s = %s and mask [O]; got %s and %d entries' % (loop, form, tuple(shape), tuple(x0.shape), mask.numel()))
+    if not bool(((mask == 0) | (mask == 1)).all()):
+        raise ValueError('%s: the mask is per %s, 0 (generate) or 1 (keep)' % (loop, unit))
+    return x0, mask
+
+
 class LayoutDenoiser:
     """UNet1DModel + GaussianDiffusion sampling on the HIP path (loop A of SURVEY.md section 3.1)."""
 
@@ -84,31 +197,10 @@ class LayoutDenoiser:
         if st is None:
             g = GraphIndex(triples, O, self.device, capacity=cap)
             b = Builder(self.device)
-            D = self.net.in_channels
-            x = b.buf(O, D)
-            step = b.buf(1, dtype=torch.int32, zero=True)
-            noise = b.buf(self.T + 1, O, D)
-            oe = b.dev(obj_embed)
-            objbuf = emit_unet1d_step(b, self.w, g, x, oe, self.temb, step, None, tables=self.tables)
-            eps = b.tags['eps']                                  # View: the output conv's K slices (the update sums the slabs)
-            n_eps_ops = len(b.ops)
-            kx0 = kmask = knoise = None
-            if keep:
-                kx0, kmask = b.buf(O, D, zero=True), b.buf(O, zero=True)
-                knoise = b.buf(self.T, O * D, zero=True)
-                b.update_keep(x, eps, self.coef, step, View(noise[1:].reshape(self.T, O * D), ld=O * D), O * D, kx0, kmask, knoise,
-                              self.keep_tab, inc_step=True, clip_x0=clip)
-            else:
-                b.update(hip.OP_DDPM, x, eps, self.coef, step, noise=View(noise[1:].reshape(self.T, O * D), ld=O * D),
-                         noise_stride=O * D, inc_step=True, clip_x0=clip)
-            plan = b.finish()
-            # eps-only plan (same ops minus the update) for step-level parity tests
-            b2 = Builder(self.device)
-            b2.ops = b.ops[:n_eps_ops]
-            b2.keep = b.keep
-            b2.tags = b.tags
-            st = dict(plan=plan, eps_plan=b2.finish(), x=x, eps=eps, step=step, noise=noise, objbuf=objbuf,
-                      oe_w=oe.shape[1], g=g, pred=b.pred_rows, sig=sig, x0=kx0, mask=kmask, knoise=knoise)
+            bufs = emit_layout_step(b, self.w, g, obj_embed, self.temb, self.tables, self.T, self.coef, self.keep_tab, clip, keep)
+            n_eps_ops = bufs.pop('n_eps_ops')
+            # 'eps_plan': the same ops minus the update, for step-level parity tests
+            st = new_state(plan=b.finish(), eps_plan=sub_plan(b, b.ops[:n_eps_ops]), g=g, sig=sig, **bufs)
             if len(self._plans) >= self.max_plans:               # a few size classes stay resident
                 self._plans.pop(next(iter(self._plans)))
             self._plans[key] = st
@@ -146,13 +238,7 @@ class LayoutDenoiser:
     def _fill_keep(self, st, x0, mask, keep_noise):
         """inputs of the masked loop into the plan's buffers (validation as ShapeDenoiser._fill_keep)"""
         O, D = st['x'].shape
-        mask = torch.as_tensor(mask, dtype=torch.float32).reshape(-1)
-        x0 = torch.as_tensor(x0)
-        if mask.numel() != O or tuple(x0.shape) != (O, D):
-            raise ValueError('masked layout loop: x0 must be [O, %d] = %s and mask [O]; got %s and %d entries'
-                             % (D, (O, D), tuple(x0.shape), mask.numel()))
-        if not bool(((mask == 0) | (mask == 1)).all()):
-            raise ValueError('masked layout loop: the mask is per node, 0 (generate) or 1 (keep)')
+        x0, mask = _check_mask(x0, mask, (O, D), 'masked layout loop', '[O, %d]' % D, 'node')
         if keep_noise is not None and (keep_noise.dim() < 2 or keep_noise.shape[0] < self.T or keep_noise[0].numel() != O * D):
             raise ValueError('masked layout loop: keep_noise must be [T, O, %d] with T = %d' % (D, self.T))
         st['x0'].copy_(x0.to(self.device).float())
@@ -173,6 +259,23 @@ class LayoutDenoiser:
         import ctypes
         hip.check(hip.lib().es_ddim_blend(ctypes.byref(a), hip.current_stream()), 'es_ddim_blend')
 
+    def stage(self, obj_embed, triples, noise=None, x0=None, mask=None, keep_noise=None, clip=False, prime=True):
+        """One call's inputs into its plan state, which is returned ready to run.  The device draws happen in THIS order (a contract:
+        a caller who seeds the generator gets the same bits from the same draws made by hand): the keep table [T, O * 8], then
+        ``noise`` [T + 1, O, 8].  ``prime``: the launch that forward-noises the kept rows of x_T (not for a run of no steps)."""
+        _check_keep_pair(x0, mask, keep_noise, 'the masked layout loop')
+        st = self._plan_for(obj_embed, triples, clip=clip, keep=mask is not None)
+        if mask is not None:
+            self._fill_keep(st, x0, mask, keep_noise)
+        if noise is None:
+            st['noise'].normal_()
+        else:
+            st['noise'][:noise.shape[0]].copy_(noise.to(self.device))
+        st['x'].copy_(st['noise'][0])
+        if mask is not None and prime:
+            self._prime_keep(st)
+        return st
+
     def sample(self, obj_embed, triples, noise=None, n_steps=None, use_graph=True, clip_denoised=False, x0=None, mask=None,
                keep_noise=None):
         """p_sample_loop_sg: returns x_0 [O, 8].  ``noise`` f32[T+1, O, 8] (row 0 = x_T, row 1+i = draw of
@@ -187,22 +290,8 @@ class LayoutDenoiser:
         like every other node; after the last iteration they are ``x0`` bit for bit.  A run stopped early (``n_steps`` < T) leaves
         them at the NEXT timestep's forward-noised value.  ``clip_denoised`` never touches kept rows.  ``mask=None``: the loop and
         its plan are what they are without this feature."""
-        if (mask is None) != (x0 is None):
-            raise ValueError('the masked layout loop needs both x0 and mask')
-        if mask is None and keep_noise is not None:
-            raise ValueError('keep_noise without a mask')
-        st = self._plan_for(obj_embed, triples, clip=bool(clip_denoised), keep=mask is not None)
-        O, D = st['x'].shape
         n_steps = self.T if n_steps is None else n_steps
-        if mask is not None:
-            self._fill_keep(st, x0, mask, keep_noise)
-        if noise is None:
-            st['noise'].normal_()
-        else:
-            st['noise'][:noise.shape[0]].copy_(noise.to(self.device))
-        st['x'].copy_(st['noise'][0])
-        if mask is not None and n_steps > 0:
-            self._prime_keep(st)
+        st = self.stage(obj_embed, triples, noise, x0, mask, keep_noise, clip=bool(clip_denoised), prime=n_steps > 0)
         st['plan'].sample(st['step'], 0, n_steps, use_graph=use_graph)
         return st['x'].clone()
 
@@ -260,6 +349,7 @@ class ShapeDenoiser:
         if sampler == 'plms':
             self._check_plms()
         self.z_shape = tuple(z_shape)
+        self.per = math.prod(int(d) for d in self.z_shape)       # elements of one object's latent
         self.temb = timestep_embedding_table(self.sched.timesteps, net.model_channels).to(self.device)
         self.coef = self.sched.coef.to(self.device)
         self.keep_tab = self.sched.keep_tab.to(self.device)      # masked DDIM: q_sample's factors per iteration (es_ddim_blend)
@@ -276,6 +366,9 @@ class ShapeDenoiser:
         self.deterministic = deterministic
         self.tables = time_tables(self.w, self.temb, self.w.shape_t, self.device)
         self._plans, self.max_plans = {}, 2
+        self._cur, self._use_graph = None, True                  # the state / graph switch the shard protocol below works on
+        # the fused (layout + shape) graph of sample_layout_and_shape, built on one of the resident plans (fused_plan)
+        self._fused, self._fused_key = None, None
 
     def _check_plms(self):
         """PLMS needs eta = 0 (PLMSSampler.make_schedule raises the same way, plms.py:28-29) and two timesteps: with one, the reference
@@ -298,10 +391,50 @@ class ShapeDenoiser:
         owns its activation buffers, split-K workspace and captured graph (several GB at O = 32)"""
         while len(self._plans) >= self.max_plans:
             old = self._plans.pop(next(iter(self._plans)))
-            fk = getattr(self, '_fused_key', None)
-            if fk is not None and old.get('plan') is not None and fk[1] == id(old['plan']):
+            if self._fused_key is not None and old['plan'] is not None and self._fused_key[1] == id(old['plan']):
                 self._fused, self._fused_key = None, None
         self._plans[key] = st
+
+    def fused_plan(self, layout_plan, ss, r):
+        """the plan of one shape step of the state ``ss`` with ``r`` steps of ``layout_plan`` on a parallel branch (plan.combine_plans).
+        One per denoiser: a caller that alternates ``shape_sampler`` per call on ONE denoiser re-captures it every call; the scene layer
+        keeps a denoiser per sampler, so each has its own."""
+        from .plan import combine_plans
+        key = (id(layout_plan), id(ss['plan']), r)
+        if self._fused_key != key:
+            self._fused, self._fused_key = combine_plans(self.device, ss['plan'], layout_plan, side_repeat=r), key
+        return self._fused
+
+    def _build_state(self, uc, triples, c, O, cap, keep, sampler, sig):
+        """a cache miss: emit the step for this rank's objects, compose its sub-plans"""
+        from .parallel import partition
+        lo, hi, block = partition(O, self.world, self.rank)
+        if hi == lo:
+            # more ranks than object blocks: this rank owns nothing.  It runs no kernels but keeps joining the
+            # collectives of the loop (a rank that raised here would leave the others blocked in the all-gather).
+            z = lambda *sh: torch.zeros(*sh, device=self.device)
+            return new_state(empty=True, x=z(0, *self.z_shape), eps=z(0, *self.z_shape), lo=lo, hi=hi, O=O, codes_local=z(block, 64),
+                             codes_all=z(block * self.world, 64), sig=sig, sampler=sampler)
+        g = GraphIndex(triples, O, self.device, capacity=cap)
+        b = Builder(self.device)
+        b.shard_block = block
+        b.force_exchange = self.force_exchange
+        if self.deterministic:
+            b.o_hint = -CANON_OBJECTS   # split-K / partial-sum tiling of the reference shard -> bit-identical latents at every world size (SURVEY 8(e))
+        plms = sampler == 'plms'
+        bufs = emit_shape_step(b, self.w, g, uc, self.temb, self.tables, self.coef, self.keep_tab, self.S, self.z_shape, lo, hi,
+                               c_local=None if c is None else c[lo:hi], gather_rows=block * self.world, keep=keep, plms=plms,
+                               step_noise=self.ddim_eta != 0.0)
+        ops = compose_step_plans(b.ops, bufs.pop('n_blend'), bufs.pop('split'), bufs.pop('n_eps_ops'), *bufs.pop('first_ops'), plms=plms,
+                                 sharded=(self.world > 1 or self.force_exchange) and self.w.mp)
+        st = new_state(lo=lo, hi=hi, O=O, g=g, sig=sig, sampler=sampler, **bufs)
+        made = {id(ops['plan']): b.finish()}                     # (the step itself owns the scratch claim; the others are views of it)
+        for name in SUB_PLANS:
+            if ops[name] is not None:
+                if id(ops[name]) not in made:
+                    made[id(ops[name])] = sub_plan(b, ops[name])
+                st[name] = made[id(ops[name])]
+        return st
 
     def _plan_for(self, uc, triples, c=None, keep=False, sampler=None):
         """``sampler='plms'``: the plans of the PLMS loop, under a cache key of their own -- 'plan' is the steady iteration (the denoiser
@@ -311,101 +444,31 @@ class ShapeDenoiser:
         ``keep=True``: the plan of the MASKED loop -- one more op, the blend (es_ddim_blend), in front of the step's denoiser ops,
         and its three inputs: ``x0`` [Ol, C,D,H,W], ``mask`` [Ol], ``knoise`` [S, Ol * latent].  A plan of its own (another cache key):
         without a mask the plan is, op for op, what it has always been."""
-        from .parallel import partition
         uc = uc.reshape(uc.shape[0], -1)
         O = uc.shape[0]
         concat = self.w.concat
-        need_c = concat or not self.w.mp        # c_s is unused only by 'crossattn' WITH message passing
-        if need_c:
+        if concat or not self.w.mp:             # c_s is unused only by 'crossattn' WITH message passing
             if c is None:
                 raise ValueError("this shape denoiser needs the conditioning c_s (concat: [O, 4096], echo2shape.py:234-235; "
                                  "no message passing: the cross-attention key [O, 1, context_dim])")
             c = c.reshape(O, -1).to(self.device).float()
+        else:
+            c = None
         cap = _cap(triples.shape[0])
         sampler = self._sampler_of(sampler)
-        plms = sampler == 'plms'
-        key = ((O, cap, 'keep') if keep else (O, cap)) + (('plms',) if plms else ())
+        key = ((O, cap, 'keep') if keep else (O, cap)) + (('plms',) if sampler == 'plms' else ())
         sig = hash(triples.detach().cpu().numpy().tobytes())
         st = self._plans.get(key)
         if st is None:
-            lo, hi, block = partition(O, self.world, self.rank)
-            if hi == lo:
-                # more ranks than object blocks: this rank owns nothing.  It runs no kernels but keeps joining the
-                # collectives of the loop (a rank that raised here would leave the others blocked in the all-gather).
-                z = lambda *sh: torch.zeros(*sh, device=self.device)
-                st = dict(empty=True, x=z(0, *self.z_shape), eps=z(0, *self.z_shape), lo=lo, hi=hi, O=O,
-                          codes_local=z(block, 64), codes_all=z(block * self.world, 64), objbuf=None, cdev=None, xc=None)
-                st['sig'], st['sampler'] = sig, sampler
-                self._insert_plan(key, st)
-                return st
-            g = GraphIndex(triples, O, self.device, capacity=cap)
-            b = Builder(self.device)
-            b.shard_block = block
-            b.force_exchange = self.force_exchange
-            if self.deterministic:
-                b.o_hint = -CANON_OBJECTS   # split-K / partial-sum tiling of the reference shard -> bit-identical latents at every world size (SURVEY 8(e))
-            x = b.buf(hi - lo, *self.z_shape)
-            eps = b.buf(hi - lo, *self.z_shape)
-            step = b.buf(1, dtype=torch.int32, zero=True)
-            kx0 = kmask = knoise = None
-            n_blend = 1 if keep else 0
-            if keep:
-                # the reference blends before p_sample_ddim (samplers/ddim.py:160-163): the denoiser -- conv-pool stem and shape GCN
-                # included -- reads the kept objects' forward-noised latents, so the generated ones are denoised in their context
-                kx0, kmask = b.buf(hi - lo, *self.z_shape, zero=True), b.buf(hi - lo, zero=True)
-                knoise = b.buf(self.S, x.numel(), zero=True)
-                b.blend(x, kx0, kmask, knoise, self.keep_tab, step)
-            ucd = b.dev(uc)
-            objbuf = emit_unet3d_step(b, self.w, g, x, ucd, self.temb, step, eps, dims=self.z_shape[1:], lo=lo, hi=hi,
-                                      c_dev=c[lo:hi] if need_c else None, tables=self.tables,
-                                      gather_rows=block * self.world)
-            n_eps_ops = len(b.ops)
-            snoise = None
-            plms_ops = None
-            if plms:
-                # the sampler's state: the last three eps, iteration i in slot i % 3, and x at the start of iteration 0
-                ring, xsave = b.buf(3, x.numel(), zero=True), b.buf(x.numel(), zero=True)
-                plms_ops = (b.plms(hip.OP_PLMS_FIRST_A, x, eps, self.coef, step, ring, xsave, push=False),
-                            b.plms(hip.OP_PLMS_FIRST_B, x, eps, self.coef, step, ring, xsave, push=False))
-                b.plms(hip.OP_PLMS, x, eps, self.coef, step, ring, xsave, inc_step=True)
-            elif self.ddim_eta != 0.0:
-                nz = x.numel()
-                snoise = b.buf(self.S, nz)
-                b.update(hip.OP_DDIM, x, eps, self.coef, step, noise=View(snoise, ld=nz), noise_stride=nz, inc_step=True)
-            else:
-                b.update(hip.OP_DDIM, x, eps, self.coef, step, inc_step=True)
-            st = dict(x=x, eps=eps, step=step, snoise=snoise, objbuf=objbuf, ucw=ucd.shape[1], lo=lo, hi=hi, O=O,
-                      codes_local=b.codes_local, codes_all=getattr(b, 'codes_all', None), code_cols=b.code_cols,
-                      xc=getattr(b, 'xc', None), g=g, pred=getattr(b, 'pred_rows', None), sig=sig,
-                      cdev=getattr(b, 'cdev', None), x0=kx0, mask=kmask, knoise=knoise, sampler=sampler)
-
-            def sub(ops):
-                b2 = Builder(self.device)
-                b2.ops, b2.keep, b2.tags = ops, b.keep, b.tags
-                b2.weight_bytes, b2.flops = b.weight_bytes, b.flops
-                return b2.finish()
-            st['plan'] = b.finish()
-            st['eps_plan'] = sub(b.ops[:n_eps_ops])
-            if (self.world > 1 or self.force_exchange) and self.w.mp:
-                st['stem_plan'] = sub(b.ops[:b.split])
-                st['main_plan'] = sub(b.ops[b.split:])
-            if plms:
-                fa, fb = plms_ops
-                den = b.ops[n_blend:n_eps_ops]
-                st['first_plan'] = sub(b.ops[:n_eps_ops] + [fa] + den + [fb])
-                if 'stem_plan' in st:
-                    # iteration 0 of the sharded loop: stem -> exchange -> rest + first-a, then once more (no blend) with first-b
-                    st['main_a_plan'] = sub(b.ops[b.split:n_eps_ops] + [fa])
-                    st['stem2_plan'] = sub(b.ops[n_blend:b.split]) if n_blend else st['stem_plan']
-                    st['main_b_plan'] = sub(b.ops[b.split:n_eps_ops] + [fb])
+            st = self._build_state(uc, triples, c, O, cap, keep, sampler, sig)
             self._insert_plan(key, st)
-        elif st.get('sig') != sig and not st.get('empty'):
+        elif st['sig'] != sig and not st['empty']:
             # same size class, another scene graph: rewrite indices / predicate rows in place, keep plans and graphs
             st['g'].update(triples)
             if st['pred'] is not None:
                 st['pred'].copy_(self.w.pred_table[torch.from_numpy(st['g'].p_host)])
             st['sig'] = sig
-        if st.get('empty'):
+        if st['empty']:
             return st
         if st['objbuf'] is not None:
             st['objbuf'][:, :st['ucw']].copy_(uc.to(self.device))
@@ -418,11 +481,11 @@ class ShapeDenoiser:
     # -- shard backend protocol of parallel.sharded_ddim_loop ------------------------------------------------
     def passes(self, i):
         """(stem -> exchange -> rest) passes of loop iteration i: 2 in iteration 0 of a PLMS loop (its second evaluation), else 1"""
-        return 2 if (self._cur.get('sampler') == 'plms' and int(i) == 0) else 1
+        return 2 if (self._cur['sampler'] == 'plms' and int(i) == 0) else 1
 
     def codes_local(self, i, p=0):
         st = self._cur
-        if not st.get('empty'):
+        if not st['empty']:
             # pass 1 (PLMS iteration 0): the stem without the blend, at the step counter first-a left (1: the reference's t_next)
             plan, first = (st['stem2_plan'], 1) if p else (st['stem_plan'], int(i))
             plan.sample(st['step'], first, 1, use_graph=self._use_graph)     # captured like the main part
@@ -436,12 +499,12 @@ class ShapeDenoiser:
 
     def step(self, i, codes_all, p=0):
         st = self._cur
-        if st.get('empty'):
+        if st['empty']:
             return
         if codes_all.data_ptr() != st['codes_all'].data_ptr():      # single-process emulations hand in their own tensor
             st['codes_all'][:codes_all.shape[0]].copy_(codes_all)
         plan, first = st['main_plan'], int(i)
-        if st.get('sampler') == 'plms' and int(i) == 0:
+        if st['sampler'] == 'plms' and int(i) == 0:
             plan, first = (st['main_b_plan'], 1) if p else (st['main_a_plan'], 0)
         plan.sample(st['step'], first, 1, use_graph=self._use_graph)
 
@@ -459,7 +522,7 @@ class ShapeDenoiser:
         regions = dict(x=st['x'], step=st['step'], coef=self.coef)
         if keep:
             regions.update(x0=st['x0'], mask=st['mask'], keep_noise=st['knoise'])
-        if st.get('snoise') is not None:
+        if st['snoise'] is not None:
             # ddim_eta != 0: the per-step draws [S, objects x latent] are an INPUT of the loop -- a named region the host fills before
             # es_shape_sample (es_model_region(m, "step_noise")); the file stores whatever the table holds now
             regions['step_noise'] = st['snoise']
@@ -480,9 +543,9 @@ class ShapeDenoiser:
         one eager all-gather per step; that matches its peers' captured ones call for call.
         Returns the graph, or None (three-call step)."""
         st = self._cur
-        if st.get('sampler') == 'plms':
+        if st['sampler'] == 'plms':
             return None                          # the captured step graph is the DDIM step; PLMS runs the three-call step
-        if not self._use_graph or ('stem_plan' not in st and not st.get('empty')) or os.environ.get('ES_STEP_GRAPH', '0') != '1':
+        if not self._use_graph or (st['stem_plan'] is None and not st['empty']) or os.environ.get('ES_STEP_GRAPH', '0') != '1':
             return None
         if 'step_graph' in st:
             return st['step_graph']
@@ -495,7 +558,7 @@ class ShapeDenoiser:
         # communicator set-up outside any capture; every rank (an empty shard too) takes part (recv is scratch)
         dist.all_gather_into_tensor(recv, send, group=group)
         torch.cuda.synchronize(self.device)
-        if not st.get('empty'):
+        if not st['empty']:
             try:
                 s = torch.cuda.Stream(device=self.device)
                 s.wait_stream(torch.cuda.current_stream(self.device))
@@ -539,36 +602,49 @@ class ShapeDenoiser:
         else:
             st['plan'].sample(st['step'], 0, n_steps, use_graph=use_graph)
 
+    def _fill_table(self, st, name, given):
+        """this rank's objects lo:hi of a per-step, per-object table [S, O, latent] into the buffer ``st[name]`` [S, (hi - lo) * latent]:
+        ``given`` by the caller, or drawn on the device.  Sharded, the table of the WHOLE scene is drawn on every rank -- also one that
+        owns no object (more ranks than objects) -- and sliced: ranks seeded alike (as they must be for noise1) draw what the
+        unsharded run draws and stay in step; a rank that skipped the draw left its generator behind the others' (ADVICE r5).  ONE
+        randn call, as the unsharded run's normal_(): a chunked draw is another Philox stream (transient: S * O * latent floats)."""
+        O, lo, hi = st['O'], st['lo'], st['hi']
+        if given is None and self.world > 1:
+            given = torch.randn(self.S, O, self.per, device=self.device)
+        if st['empty']:
+            return
+        if given is None:
+            st[name].normal_()
+        else:
+            t = given.to(self.device).float().reshape(given.shape[0], O, self.per)[:self.S, lo:hi]
+            st[name][:t.shape[0]].copy_(t.reshape(t.shape[0], -1))
+
     def _fill_keep(self, st, x0, mask, keep_noise):
         """inputs of the masked loop into the plan's buffers (this rank's objects lo:hi of the scene's)"""
         O, lo, hi = st['O'], st['lo'], st['hi']
-        per = 1
-        for d in self.z_shape:
-            per *= int(d)
-        mask = torch.as_tensor(mask, dtype=torch.float32).reshape(-1)
-        if mask.numel() != O or tuple(x0.shape) != (O,) + tuple(self.z_shape):
-            raise ValueError('masked DDIM: x0 must be [O, C, D, H, W] = %s and mask [O]; got %s and %d entries'
-                             % ((O,) + tuple(self.z_shape), tuple(x0.shape), mask.numel()))
-        if not bool(((mask == 0) | (mask == 1)).all()):
-            raise ValueError('masked DDIM: the mask is per object, 0 (generate) or 1 (keep)')
-        if keep_noise is not None and (keep_noise.shape[0] < self.S or keep_noise[0].numel() != O * per):
+        x0, mask = _check_mask(x0, mask, (O,) + self.z_shape, 'masked DDIM', '[O, C, D, H, W]', 'object')
+        if keep_noise is not None and (keep_noise.shape[0] < self.S or keep_noise[0].numel() != O * self.per):
             raise ValueError('masked DDIM: keep_noise must be [S, O, C, D, H, W]')
-        full = None
-        if keep_noise is None and self.world > 1:
-            # the table of the WHOLE scene on every rank (an empty one too), then this rank's objects: as the step_noise branch
-            # does, and for the same reason -- ranks seeded alike draw what the unsharded run draws and stay in step
-            full = torch.randn(self.S, O, per, device=self.device)
-        if st.get('empty'):
-            return
-        st['x0'].copy_(x0.to(self.device).float()[lo:hi])
-        st['mask'].copy_(mask.to(self.device)[lo:hi])
-        if full is not None:
-            st['knoise'].copy_(full[:, lo:hi].reshape(self.S, -1))
-        elif keep_noise is None:
-            st['knoise'].normal_()
-        else:
-            kn = keep_noise.to(self.device).float().reshape(keep_noise.shape[0], O, per)[:self.S, lo:hi]
-            st['knoise'].copy_(kn.reshape(self.S, -1))
+        if not st['empty']:
+            st['x0'].copy_(x0.to(self.device).float()[lo:hi])
+            st['mask'].copy_(mask.to(self.device)[lo:hi])
+        self._fill_table(st, 'knoise', keep_noise)
+
+    def stage(self, uc, triples, c=None, noise1=None, step_noise=None, x0=None, mask=None, keep_noise=None, sampler=None):
+        """One call's inputs into its plan state, which is returned ready to run.  The device draws happen in THIS order (a contract:
+        ranks seeded alike stay in step, and a caller who seeds the generator gets the same bits from the same draws made by hand):
+        the keep table [S, O * latent], then ``noise1`` [1, C, D, H, W], then ``step_noise`` [S, O * latent] (eta != 0 only); sharded, the
+        two tables are those of the whole scene on every rank (_fill_table)."""
+        _check_keep_pair(x0, mask, keep_noise, 'masked DDIM')
+        st = self._plan_for(uc, triples, c, keep=mask is not None, sampler=sampler)
+        if mask is not None:
+            self._fill_keep(st, x0, mask, keep_noise)
+        if noise1 is None:
+            noise1 = torch.randn((1,) + self.z_shape, device=self.device)
+        st['x'].copy_(noise1.to(self.device).expand(st['hi'] - st['lo'], *self.z_shape))
+        if self.ddim_eta != 0.0:
+            self._fill_table(st, 'snoise', step_noise)
+        return st
 
     def sample(self, uc, triples, noise1=None, n_steps=None, use_graph=True, c=None, step_noise=None, x0=None, mask=None,
                keep_noise=None, sampler=None):
@@ -587,53 +663,18 @@ class ShapeDenoiser:
         evaluates the denoiser twice (improved Euler), so k iterations are k + 1 evaluations; the masked loop blends once per iteration,
         before its first evaluation.
         Returns the latents of ALL objects [O,C,D,H,W] (all-gathered when sharded)."""
-        from .parallel import sharded_ddim_loop
-        if (mask is None) != (x0 is None):
-            raise ValueError('masked DDIM needs both x0 and mask')
-        if mask is None and keep_noise is not None:
-            raise ValueError('keep_noise without a mask')
-        st = self._plan_for(uc, triples, c, keep=mask is not None, sampler=sampler)
-        if mask is not None:
-            self._fill_keep(st, x0, mask, keep_noise)
+        from .parallel import all_gather_rows, sharded_ddim_loop
+        st = self.stage(uc, triples, c, noise1, step_noise, x0, mask, keep_noise, sampler)
         n_steps = self.S if n_steps is None else n_steps
-        if noise1 is None:
-            noise1 = torch.randn((1,) + self.z_shape, device=self.device)
-        st['x'].copy_(noise1.to(self.device).expand(st['hi'] - st['lo'], *self.z_shape))
-        if st.get('snoise') is not None or (self.ddim_eta != 0.0 and st.get('empty')):
-            if step_noise is None and self.world > 1:
-                # one table for the WHOLE scene from this rank's generator, then this rank's objects: ranks seeded alike (as they
-                # must be for noise1) draw what the unsharded run draws -- a local normal_() gave every world size its own noise
-                # EVERY rank draws the table, also one that owns no object (more ranks than objects): a rank that skipped the draw left
-                # its generator behind the others', and the next call's noise1 differed between ranks (ADVICE r5).  One call for the
-                # whole table, as the unsharded run's normal_() -- a chunked draw is another Philox stream (transient: S*O*latent floats)
-                per = 1
-                for d in self.z_shape:
-                    per *= int(d)
-                full = torch.randn(self.S, st['O'], per, device=self.device)
-                if st['hi'] > st['lo']:
-                    st['snoise'].copy_(full[:, st['lo']:st['hi']].reshape(self.S, -1))
-                del full
-            elif st.get('snoise') is None:
-                pass                                 # (an empty shard with a caller-given table: nothing to fill)
-            elif step_noise is None:
-                st['snoise'].normal_()
-            else:
-                sn = step_noise.to(self.device).float()[:, st['lo']:st['hi']]
-                st['snoise'][:sn.shape[0]].copy_(sn.reshape(sn.shape[0], -1))
-        if st.get('empty'):
-            from .parallel import all_gather_rows, sharded_ddim_loop as loop
-            if not self.w.mp:
-                return all_gather_rows(st['x'], st['O'], self.world, self.group).clone()
+        if not self.w.mp or (self.world == 1 and not self.force_exchange):
+            # no exchange inside the loop: each rank runs its own objects (no message passing: ranks only meet at the end)
+            if not st['empty']:
+                self._run_loop(st, n_steps, use_graph)
+            z = st['x'] if self.world == 1 else all_gather_rows(st['x'], st['O'], self.world, self.group)
+        else:
             self._cur, self._use_graph = st, use_graph
-            return loop(self, st['O'], n_steps, self.world, self.group).clone()
-        if (self.world == 1 and not self.force_exchange) or not self.w.mp:
-            self._run_loop(st, n_steps, use_graph)
-            if self.world == 1:
-                return st['x'].clone()
-            from .parallel import all_gather_rows         # no message passing: ranks only meet at the end
-            return all_gather_rows(st['x'], st['O'], self.world, self.group).clone()
-        self._cur, self._use_graph = st, use_graph
-        return sharded_ddim_loop(self, st['O'], n_steps, self.world, self.group).clone()
+            z = sharded_ddim_loop(self, st['O'], n_steps, self.world, self.group)
+        return z.clone()
 
 
 def keep_selection(keep_nodes, n_objects):
@@ -664,52 +705,46 @@ def sample_layout_and_shape(lay, shp, obj_embed, triples, uc, c=None, layout_noi
     the masked layout loop (LayoutDenoiser.sample) -- its keep plan is then the side branch of the fused graph and runs the left-over
     steps; the two families are independent of each other.
     ``shape_sampler``: 'ddim' / 'plms' for the shape loop (None: the denoiser's own).  PLMS: iteration 0 (two evaluations) runs unfused,
-    iterations 1..S-1 replay the fused graph, and the layout steps not covered run afterwards."""
-    from .plan import combine_plans
-    if (box_mask is None) != (box_x0 is None):
-        raise ValueError('the masked layout loop needs both box_x0 and box_mask')
-    if box_mask is None and box_keep_noise is not None:
-        raise ValueError('box_keep_noise without a box_mask')
+    iterations 1..S-1 replay the fused graph, and the layout steps not covered run afterwards.
+    Inputs are staged layout first, then shape (LayoutDenoiser.stage, ShapeDenoiser.stage: the order of the device draws); a
+    ``ddim_eta`` != 0 shape denoiser draws its step-noise table last (this call has no argument to pass that table in)."""
+    _check_keep_pair(box_x0, box_mask, box_keep_noise, 'the masked layout loop', 'box_')
     if shp.world != 1:
         return lay.sample(obj_embed, triples, noise=layout_noise, use_graph=use_graph, x0=box_x0, mask=box_mask,
                           keep_noise=box_keep_noise), \
             shp.sample(uc, triples, noise1=shape_noise, c=c, use_graph=use_graph, x0=x0, mask=mask, keep_noise=keep_noise,
                        sampler=shape_sampler)
-    st = lay._plan_for(obj_embed, triples, keep=box_mask is not None)
-    if box_mask is not None:
-        lay._fill_keep(st, box_x0, box_mask, box_keep_noise)
-    if layout_noise is None:
-        st['noise'].normal_()
-    else:
-        st['noise'][:layout_noise.shape[0]].copy_(layout_noise.to(lay.device))
-    st['x'].copy_(st['noise'][0])
-    if box_mask is not None:
-        lay._prime_keep(st)
-    ss = shp._plan_for(uc, triples, c, keep=mask is not None, sampler=shape_sampler)
-    plms = ss['sampler'] == 'plms'
-    if mask is not None:
-        shp._fill_keep(ss, x0, mask, keep_noise)
-    if shape_noise is None:
-        shape_noise = torch.randn((1,) + shp.z_shape, device=shp.device)
-    ss['x'].copy_(shape_noise.to(shp.device).expand(ss['hi'] - ss['lo'], *shp.z_shape))
+    st = lay.stage(obj_embed, triples, layout_noise, box_x0, box_mask, box_keep_noise)
+    ss = shp.stage(uc, triples, c, shape_noise, None, x0, mask, keep_noise, shape_sampler)
+    first = 1 if ss['sampler'] == 'plms' else 0                 # PLMS: iteration 0 is not a replay of the steady step
     r = lay.T // shp.S
     done = 0
     if r >= 1 and use_graph:
-        key = (id(st['plan']), id(ss['plan']), r)
-        # (one fused graph per shape denoiser: a caller that alternates ``shape_sampler`` per call on ONE denoiser re-captures it every
-        #  call; the scene layer keeps a denoiser per sampler, so each has its own)
-        if getattr(shp, '_fused_key', None) != key:
-            shp._fused, shp._fused_key = combine_plans(shp.device, ss['plan'], st['plan'], side_repeat=r), key
+        fused = shp.fused_plan(st['plan'], ss, r)
         st['step'].zero_()
-        if plms:
+        if first:
             ss['first_plan'].sample(ss['step'], 0, 1, use_graph=True)
-        shp._fused.sample(ss['step'], 1 if plms else 0, shp.S - (1 if plms else 0), use_graph=True)
-        done = r * (shp.S - (1 if plms else 0))
+        fused.sample(ss['step'], first, shp.S - first, use_graph=True)
+        done = r * (shp.S - first)
     else:
         shp._run_loop(ss, shp.S, use_graph)
     if done < lay.T:
         st['plan'].sample(st['step'], done, lay.T - done, use_graph=use_graph)
     return st['x'].clone(), ss['x'].clone()
+
+
+def _run_chunks(codec, src, out, dims, src_key, dst_key, sync):
+    """the chunk loop of VQDecoder / VQEncoder: ``codec.chunk`` objects of ``src`` at a time through the plan of that many objects
+    (its input buffer ``src_key``, its result ``dst_key``) into ``out``"""
+    for i in range(0, src.shape[0], codec.chunk):
+        n = min(codec.chunk, src.shape[0] - i)
+        st = codec._plan(n, dims)
+        st[src_key].copy_(src[i:i + n])
+        st['plan'].run()
+        out[i:i + n].copy_(st[dst_key])
+    if sync:
+        torch.cuda.synchronize()
+    return out
 
 
 class VQDecoder:
@@ -748,15 +783,7 @@ class VQDecoder:
         zdims = tuple(z.shape[2:])
         n_up = len([1 for _, up in self.w.levels if up is not None])
         out = torch.empty(O, 1, *[d * 2 ** n_up for d in zdims], device=self.device)
-        for i in range(0, O, self.chunk):
-            n = min(self.chunk, O - i)
-            st = self._plan(n, zdims)
-            st['z'].copy_(z[i:i + n])
-            st['plan'].run()
-            out[i:i + n].copy_(st['sdf'])
-        if sync:
-            torch.cuda.synchronize()
-        return out
+        return _run_chunks(self, z, out, zdims, 'z', 'sdf', sync)
 
 
 class VQEncoder:
@@ -804,12 +831,4 @@ class VQEncoder:
         O = sdf.shape[0]
         dims = tuple(sdf.shape[2:])
         out = torch.empty(O, self.w.embed_dim, *[d >> self.w.n_down for d in dims], device=self.device)
-        for i in range(0, O, self.chunk):
-            n = min(self.chunk, O - i)
-            st = self._plan(n, dims)
-            st['sdf'].copy_(sdf[i:i + n])
-            st['plan'].run()
-            out[i:i + n].copy_(st['z'])
-        if sync:
-            torch.cuda.synchronize()
-        return out
+        return _run_chunks(self, sdf, out, dims, 'sdf', 'z', sync)

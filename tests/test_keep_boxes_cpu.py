@@ -109,12 +109,13 @@ def test_layout_schedule_q_sample_columns_equal_the_reference_tables(T):
 
 # ------------------------------------------------------------------------------------------------ plans, without a device
 def dry_layout_ops(keep=False, clip=False, O=8, T=100, mc=128):
-    """The op list LayoutDenoiser._plan_for builds, emitted by a CPU Builder (tools/plan_dryrun.py's way: no plan is created, nothing
-    runs): one UNet1D step with per-schedule tables and the K-sliced output conv, then the update op.  Returns (ops, n_launches)."""
-    from echoscene_amd import synth, config as escfg, hip
+    """The op list LayoutDenoiser._plan_for builds -- samplers.emit_layout_step, the function it calls -- emitted by a CPU Builder
+    (tools/plan_dryrun.py's way: no plan is created, nothing runs): one UNet1D step with per-schedule tables and the K-sliced output
+    conv, then the update op."""
+    from echoscene_amd import synth, config as escfg
     from echoscene_amd.model.unet import UNet1DModel
-    from echoscene_amd.plan import Builder, GraphIndex, UNet1DWeights, View, emit_unet1d_step
-    from echoscene_amd.samplers import _cap, _cpu_sd
+    from echoscene_amd.plan import Builder, GraphIndex, UNet1DWeights
+    from echoscene_amd.samplers import _cap, _cpu_sd, emit_layout_step
     from echoscene_amd.schedules import LayoutSchedule
     dev = torch.device('cpu')
     net = UNet1DModel(**escfg.layout_denoiser_kwargs(mc))
@@ -124,20 +125,8 @@ def dry_layout_ops(keep=False, clip=False, O=8, T=100, mc=128):
     g = GraphIndex(triples, O, dev, capacity=_cap(triples.shape[0]))
     sched = LayoutSchedule(T)
     b = Builder(dev)
-    D = net.in_channels
-    x = b.buf(O, D)
-    step = b.buf(1, dtype=torch.int32, zero=True)
-    noise = b.buf(T + 1, O, D)
-    oe = b.dev(torch.zeros(O, 640))
     tables = dict(emb=None, emb_all=torch.zeros(T, w.emb_all.N), t_lin=torch.zeros(T, 64))
-    emit_unet1d_step(b, w, g, x, oe, torch.zeros(T, mc), step, None, tables=tables)
-    eps = b.tags['eps']
-    nz = View(noise[1:].reshape(T, O * D), ld=O * D)
-    if keep:
-        b.update_keep(x, eps, sched.coef, step, nz, O * D, b.buf(O, D, zero=True), b.buf(O, zero=True), b.buf(T, O * D, zero=True),
-                      sched.keep_tab, inc_step=True, clip_x0=clip)
-    else:
-        b.update(hip.OP_DDPM, x, eps, sched.coef, step, noise=nz, noise_stride=O * D, inc_step=True, clip_x0=clip)
+    emit_layout_step(b, w, g, torch.zeros(O, 640), torch.zeros(T, mc), tables, T, sched.coef, sched.keep_tab, clip=clip, keep=keep)
     return b.ops
 
 

@@ -263,3 +263,34 @@ def test_sharded_plms_loop_joins_s_plus_1_all_gathers_on_every_rank(tmp_path, wo
     sharded_ddim_loop(d, O, S, 1)
     assert d.trace == [(k, i, 0) for i in range(S) for k in ('codes', 'step')]
     assert not torch.equal(d.x, ref.x)
+
+
+# ------------------------------------------------------------------------------------------------ sub-plan composition
+@pytest.mark.parametrize('sharded', [False, True])
+@pytest.mark.parametrize('plms', [False, True])
+@pytest.mark.parametrize('n_blend', [0, 1])
+def test_sub_plans_are_slices_of_the_step(n_blend, plms, sharded):
+    """samplers.compose_step_plans on plain integers for ops (no library, no device): the identities the GPU tests assert on the
+    plans a ShapeDenoiser really runs (tests/test_hip_plms.py, tests/test_hip_keep.py, tests/test_hip_vol.py)."""
+    from echoscene_amd.samplers import SUB_PLANS, compose_step_plans
+    plan, split, n_eps_ops, A, B = list(range(11)), 4, 10, 100, 101      # 10 denoiser ops (the first: the blend, if any) + the sampler op
+    p = compose_step_plans(plan, n_blend, split, n_eps_ops, A, B, plms=plms, sharded=sharded)
+    assert set(p) == set(SUB_PLANS)
+    assert p['plan'] == plan and p['eps_plan'] == plan[:-1]
+    if sharded:
+        stem, main = p['stem_plan'], p['main_plan']
+        assert stem + main == plan and stem == plan[:split]
+    else:
+        assert p['stem_plan'] is None and p['main_plan'] is None
+    if plms:
+        assert p['first_plan'] == plan[:-1] + [A] + plan[n_blend:-1] + [B]
+    else:
+        assert p['first_plan'] is None
+    if plms and sharded:
+        assert p['stem2_plan'] == stem[n_blend:] and (p['stem2_plan'] is stem) == (n_blend == 0)
+        assert p['main_a_plan'] == main[:-1] + [A] and p['main_b_plan'] == main[:-1] + [B]
+        # the two passes of iteration 0 are the unsharded first plan, cut at the exchange
+        assert stem + p['main_a_plan'] + p['stem2_plan'] + p['main_b_plan'] == p['first_plan']
+    else:
+        assert p['main_a_plan'] is None and p['stem2_plan'] is None and p['main_b_plan'] is None
+    assert plan == list(range(11)), 'the step itself is not modified'

@@ -12,10 +12,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def emit_layout_step_cpu(mc=128, O=8, enable_t_emb=True, concat=False, seed=3):
-    from echoscene_amd import synth, config as escfg, hip
+    """the denoiser of the layout loop step (samplers.emit_layout_step without the update, eps as a plain tensor) on a CPU Builder"""
+    from echoscene_amd import synth, config as escfg
     from echoscene_amd.model.unet import UNet1DModel
-    from echoscene_amd.plan import Builder, GraphIndex, UNet1DWeights, emit_unet1d_step
-    from echoscene_amd.samplers import _cap, _cpu_sd
+    from echoscene_amd.plan import Builder, GraphIndex, UNet1DWeights
+    from echoscene_amd.samplers import _cap, _cpu_sd, emit_layout_step
     dev = torch.device('cpu')
     net = UNet1DModel(**escfg.layout_denoiser_kwargs(mc, enable_t_emb=enable_t_emb, concat=concat))
     synth.seeded_fill_(net, prefix='dry.')
@@ -23,15 +24,11 @@ def emit_layout_step_cpu(mc=128, O=8, enable_t_emb=True, concat=False, seed=3):
     _, triples = synth.synthetic_graph(O, seed=seed)
     g = GraphIndex(triples, O, dev, capacity=_cap(triples.shape[0]))
     b = Builder(dev)
-    x = b.buf(O, net.in_channels)
     eps = b.buf(O, net.out_channels)
-    step = b.buf(1, dtype=torch.int32, zero=True)
-    oe = b.dev(torch.randn(O, 640))
     n_steps = 4
     tables = dict(emb=None, emb_all=torch.zeros(n_steps, w.emb_all.N), t_lin=torch.zeros(n_steps, 64) if enable_t_emb else None)
-    temb = torch.zeros(n_steps, mc)
-    emit_unet1d_step(b, w, g, x, oe, temb, step, eps, tables=tables)
-    return b, dict(x=x, eps=eps, step=step)
+    bufs = emit_layout_step(b, w, g, torch.randn(O, 640), torch.zeros(n_steps, mc), tables, n_steps, eps_out=eps)
+    return b, dict(x=bufs['x'], eps=eps, step=bufs['step'])
 
 
 def _linear_io(a, hip):
