@@ -523,7 +523,9 @@ __device__ __forceinline__ void* uniform_ptr(const void* p) {
 // EPI_: -1 = a.epilogue decides at run time (general kernels); ES_EPI_NONE / ES_EPI_GEGLU = compiled for that epilogue only
 // (k_conv_ws: with both paths in one function the register allocator spilled 150-250 dwords at the 168-register cap).
 // STATS_ (LOWREG only): besides storing the tile, form the row-group sums of es_conv_args.gn_stats_out from the stored values.
-template <int BM_, int NW_, bool ACTIVE = true, bool LOWREG = false, int EPI_ = -1, bool NOSYNC = false, bool STATS_ = false>      // ACTIVE = false: a producer wave of k_conv_ws, joins the barriers only
+// FOLD_ (LOWREG only, k_conv_ws_fold): the tile's rows run (parity class, d, hi, wi) inside an object instead of (d, h, w); a row goes
+// to output voxel (d, 2 hi + ph, 2 wi + pw), so the tensors keep the canonical [O, D, H, W, C] layout.
+template <int BM_, int NW_, bool ACTIVE = true, bool LOWREG = false, int EPI_ = -1, bool NOSYNC = false, bool STATS_ = false, bool FOLD_ = false>      // ACTIVE = false: a producer wave of k_conv_ws, joins the barriers only
 __device__ __forceinline__ void conv_epilogue(const es_conv_args& a, const ConvGeom& g, f4 (&acc)[BM_ / (NW_ / 2) / 16][7],
                                               char* smem, long M, long m0, int n0, int wave, int lane, int S, int bz,
                                               int ncdhw) {
@@ -645,18 +647,33 @@ __device__ __forceinline__ void conv_epilogue(const es_conv_args& a, const ConvG
             // pieces now and then at 4 objects per GPU -- the only shape that sends them through k_conv_ws -- whenever the
             // compiler reused the offset SGPR right behind the store; with the offset folded into the VGPR the runs are clean.)
             const unsigned ldp = part ? (unsigned)a.N : ld;
-            float* const o32 = part ? part + mw0 * (long)a.N : (a.out_f32 ? a.out_f32 + mw0 * (long)a.out_ld : nullptr);
+            // FOLD_: the descriptors start at the object's first voxel.  Row r = (d, hi, wi) of class (ph, pw) is voxel
+            // (d, 2 hi + ph, 2 wi + pw) = 4 r - 2 (r & (Wi - 1)) + ph W + pw of the object: fold_off() is the fp32 byte offset of this
+            // lane's row (i, t) -- one per-lane base and, per row, an add, an and and a multiply-add
+            const unsigned fold_rem = FOLD_ ? (unsigned)(mw0 & ((1L << vsh) - 1)) : 0u;      // the wave's first row inside its object, (class, d, hi, wi) order
+            const long mb0 = mw0 - (long)fold_rem;
+            const unsigned fold_r0 = (fold_rem & ((1u << (vsh - 2)) - 1u)) + (unsigned)rsub;
+            const unsigned fold_base = FOLD_ ? ((4u * fold_r0 + (((fold_rem >> (vsh - 1)) & 1u) << g.lw) + ((fold_rem >> (vsh - 2)) & 1u)) * ld + (unsigned)n) * 4u : 0u;
+            auto fold_off = [&](int i, int t) __attribute__((always_inline)) {
+                return fold_base + (unsigned)(i * 16 + 2 * t) * ld * 16u - ((fold_r0 + (unsigned)(i * 16 + 2 * t)) & (unsigned)(g.Wi - 1)) * (ld * 8u);
+            };
+            float* const o32 = part ? part + mb0 * (long)a.N : (a.out_f32 ? a.out_f32 + mb0 * (long)a.out_ld : nullptr);
             const __amdgpu_buffer_rsrc_t rO32 = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(o32), (short)0, o32 ? (int)OOBV : 0, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rO16 = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr((!part && a.out_f16) ? (_Float16*)a.out_f16 + mw0 * (long)a.out_ld : nullptr), (short)0, (!part && a.out_f16) ? (int)OOBV : 0, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rRes = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(use_res ? a.res + mw0 * (long)a.out_ld : nullptr), (short)0, use_res ? (int)OOBV : 0, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rO16 = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr((!part && a.out_f16) ? (_Float16*)a.out_f16 + mb0 * (long)a.out_ld : nullptr), (short)0, (!part && a.out_f16) ? (int)OOBV : 0, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rRes = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(use_res ? a.res + mb0 * (long)a.out_ld : nullptr), (short)0, use_res ? (int)OOBV : 0, 0x00020000);
             const int rsub_l = lane < 56 ? rsub : 0;                              // (idle lanes read a valid LDS row)
             const unsigned vrow32 = n_ok ? ((unsigned)rsub * ldp + (unsigned)n) * 4u : OOBV;
             const unsigned vrow16 = n_ok ? ((unsigned)rsub * ld + (unsigned)n) * 2u : OOBV;
             auto load_res_s = [&](int i, f4 (&rr)[8]) __attribute__((always_inline)) {
 #pragma unroll
                 for (int t = 0; t < 8; ++t) {
+                    if constexpr (FOLD_) {
+                        const unsigned vo = (n_ok && i * 16 + rsub + 2 * t < rows_left) ? fold_off(i, t) : OOBV;
+                        rr[t] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rRes, (int)vo, 0, 0));
+                    } else {
                     const unsigned vo = (i * 16 + rsub + 2 * t < rows_left) ? vrow32 + (unsigned)(i * 16 + 2 * t) * ld * 4u : OOBV;
                     rr[t] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rRes, (int)vo, 0, 0));
+                    }
                 }
             };
             auto combine_s = [&](int i, const f4 (&rr)[8]) __attribute__((always_inline)) {
@@ -667,9 +684,16 @@ __device__ __forceinline__ void conv_epilogue(const es_conv_args& a, const ConvG
                     v += bias4;
                     v += rv4;
                     v += rr[t];
+                    if constexpr (FOLD_) {
+                        const unsigned e4 = fold_off(i, t);
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, v), rO32, (int)((ok && n_ok) ? e4 : OOBV), 0, 0);
+                        const h4 hv = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
+                        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, hv), rO16, (int)((ok && n_ok) ? e4 >> 1 : OOBV), 0, 0);
+                    } else {
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, v), rO32, (int)(ok ? vrow32 + (unsigned)(i * 16 + 2 * t) * ldp * 4u : OOBV), 0, 0);
                     const h4 hv = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
                     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, hv), rO16, (int)(ok ? vrow16 + (unsigned)(i * 16 + 2 * t) * ld * 2u : OOBV), 0, 0);
+                    }
                     if constexpr (STATS_) {
                         gs += v;
 #pragma unroll
@@ -1189,7 +1213,12 @@ __device__ __forceinline__ void wait_ahead(int ahead) {
     }
 }
 
-template <int BM_, int NC_, int NP_, bool UP_, int EPI_, bool STATS_, int NS_ = 3>
+// FOLD_ (k_conv_ws_fold, ES_CONV_UP_HW with the folded weight image in a.w2): 12 K units per channel chunk instead of 27.  The rows of
+// an object run (parity class 2 ph + pw, d, hi, wi); a 256-row tile is one class of one object (the host routes D Hi Wi % 256 == 0
+// here), and folded tap (kd, jh, jw) of class (ph, pw) is addressed as tap (kd, jh - 1 + ph, jw - 1 + pw) of the 27 -- the one source
+// voxel that the taps summed into its weight all read -- so the gather, the zero padding (tap_mask27 on output coordinates: a tap that
+// falls outside stands alone in its folded slot) and the nearest-up shifts are the 27-tap ones.
+template <int BM_, int NC_, int NP_, bool UP_, int EPI_, bool STATS_, int NS_ = 3, bool FOLD_ = false>
 __device__ __forceinline__ void conv_ws_tile(const es_conv_args& a, const ConvGeom& g, int ncdhw, char* smem, const int wave, const int lane,
                                              const long M, const int bx, const int by, const int ks_begin, const int ks_end,
                                              const int S, const int bz, unsigned long long* stamp) {
@@ -1208,9 +1237,13 @@ __device__ __forceinline__ void conv_ws_tile(const es_conv_args& a, const ConvGe
     const long m0 = (long)bx * BM_;
     const int n0 = by * BN;
     const int kch0 = a.Cin >> 5;
-    const int nks0 = a.taps * kch0;
+    const int ntap0 = FOLD_ ? 12 : a.taps;
+    const int nks0 = ntap0 * kch0;
     const int nloc = ks_end - ks_begin;                           // K units of this workgroup
     const int nstage = (nloc + UPS_ - 1) / UPS_;
+    static_assert(!FOLD_ || UP_, "the folded taps are those of a nearest-up conv");
+    const int fold_cls = FOLD_ ? (int)((m0 >> (g.lw + g.lh + g.ld - 2)) & 3) : 0;       // (the whole tile is one class)
+    const int fold_ph = fold_cls >> 1, fold_pw = fold_cls & 1;
     if (wave >= NC_) {
         // =============================== producer ===============================
         const int pw = wave - NC_;
@@ -1228,11 +1261,16 @@ __device__ __forceinline__ void conv_ws_tile(const es_conv_args& a, const ConvGe
             a_h[j] = (int)((mm >> g.lw) & (g.H - 1));
             a_d[j] = (int)((mm >> (g.lw + g.lh)) & (g.D - 1));
             a_o[j] = (int)(mm >> (g.lw + g.lh + g.ld));
+            if constexpr (FOLD_) {
+                a_w[j] = 2 * (int)(mm & (g.Wi - 1)) + fold_pw;
+                a_h[j] = 2 * (int)((mm >> (g.lw - 1)) & (g.Hi - 1)) + fold_ph;
+                a_d[j] = (int)((mm >> (g.lw + g.lh - 2)) & (g.D - 1));
+            }
         }
         int st_phase = ks_begin >= nks0 ? 1 : 0;
-        int st_tap = st_phase ? 0 : ks_begin % a.taps;
-        int st_c = st_phase ? (ks_begin - nks0) : (ks_begin / a.taps);
-        int st_ntap = st_phase ? 1 : a.taps, st_kch = st_phase ? (a.Cin2 >> 5) : kch0;
+        int st_tap = st_phase ? 0 : ks_begin % ntap0;
+        int st_c = st_phase ? (ks_begin - nks0) : (ks_begin / ntap0);
+        int st_ntap = st_phase ? 1 : ntap0, st_kch = st_phase ? (a.Cin2 >> 5) : kch0;
         unsigned st_boff = (unsigned)(st_phase ? (ks_begin - nks0) : ks_begin) * (unsigned)B_BYTES;
         unsigned voff[NA], msk[NA];
         int upm[NA][3], upp[NA][3];
@@ -1241,6 +1279,7 @@ __device__ __forceinline__ void conv_ws_tile(const es_conv_args& a, const ConvGe
         auto set_phase = [&]() __attribute__((always_inline)) {
             const _Float16* Wg = (const _Float16*)(st_phase ? a.w2 : a.w);
             const long nks_ph = st_phase ? (long)(a.Cin2 >> 5) : (long)nks0;
+            if constexpr (FOLD_) Wg = (const _Float16*)a.w2 + ((long)fold_cls * ((a.N + BN - 1) / BN) * nks0) * (BNP * BK);      // the class's image
             rB = __builtin_amdgcn_make_buffer_rsrc((void*)(Wg + ((long)by * nks_ph) * (BNP * BK)), (short)0, (int)OOB, 0x00020000);
             const _Float16* Ag = (const _Float16*)(st_phase ? a.a2 : a.a);
             const int Cin = st_phase ? a.Cin2 : a.Cin;
@@ -1289,10 +1328,12 @@ __device__ __forceinline__ void conv_ws_tile(const es_conv_args& a, const ConvGe
         ES_STAMP_AT(1);
         const unsigned voffB = (unsigned)lane * 16u;
         auto issue_unit = [&](char* dst) __attribute__((always_inline)) {        // dst: LDS base of the unit (A tile, then B tile)
-            const unsigned sA = (unsigned)__builtin_amdgcn_readlane(dtab, st_tap) + (unsigned)st_c * 64u;
-            const unsigned sbit = 1u << st_tap;
+            int tap27 = st_tap;
+            if constexpr (FOLD_) tap27 = (st_tap >> 2) * 9 + (((st_tap >> 1) & 1) + fold_ph) * 3 + (st_tap & 1) + fold_pw;
+            const unsigned sA = (unsigned)__builtin_amdgcn_readlane(dtab, tap27) + (unsigned)st_c * 64u;
+            const unsigned sbit = 1u << tap27;
             int ukd = 0, ukh = 0, ukw = 0;
-            if (UP_) { ukd = st_tap / 9 - 1; ukh = (st_tap / 3) % 3 - 1; ukw = st_tap % 3 - 1; }
+            if (UP_) { ukd = tap27 / 9 - 1; ukh = (tap27 / 3) % 3 - 1; ukw = tap27 % 3 - 1; }
 #pragma unroll
             for (int j = 0; j < NA; ++j) {
                 unsigned vs = voff[j];
@@ -1344,7 +1385,7 @@ __device__ __forceinline__ void conv_ws_tile(const es_conv_args& a, const ConvGe
         }
         ES_STAMP_AT(3);
         f4 dummy[MI][7];
-        conv_epilogue<BM_, NC_, false, true, EPI_, false, STATS_>(a, g, dummy, smem, M, m0, n0, wave, lane, S, bz, ncdhw);
+        conv_epilogue<BM_, NC_, false, true, EPI_, false, STATS_, FOLD_>(a, g, dummy, smem, M, m0, n0, wave, lane, S, bz, ncdhw);
         ES_STAMP_AT(4);
         return;
     }
@@ -1405,7 +1446,7 @@ __device__ __forceinline__ void conv_ws_tile(const es_conv_args& a, const ConvGe
         ws_mma<MI>(acc, af, bfr);                                               // last unit
     }
     ES_STAMP_AT(3);
-    conv_epilogue<BM_, NC_, true, true, EPI_, false, STATS_>(a, g, acc, smem, M, m0, n0, wave, lane, S, bz, ncdhw);
+    conv_epilogue<BM_, NC_, true, true, EPI_, false, STATS_, FOLD_>(a, g, acc, smem, M, m0, n0, wave, lane, S, bz, ncdhw);
     ES_STAMP_AT(4);
 }
 
@@ -1426,6 +1467,26 @@ __global__ __launch_bounds__(64 * (NC_ + NP_), 3) void k_conv_ws(const es_conv_a
     int ks_begin, ks_end;
     split_range(a.taps * (a.Cin >> 5), a.a2 ? (a.Cin2 >> 5) : 0, a.taps, bz, S, ks_begin, ks_end);
     conv_ws_tile<BM_, NC_, NP_, UP_, EPI_, STATS_, NS_>(a, g, ncdhw, smem, wave, lane, M, bx, by, ks_begin, ks_end, S, bz, stamp);
+}
+
+// k_conv_ws<256, 8, 4, UP_> on the folded weight image of an ES_CONV_UP_HW conv (es_conv_args.w2, es_pack_conv_up_fold_f16): after
+// nearest x2 two of the three taps along H, and two of three along W, read the same input voxel, so per output parity (h & 1, w & 1)
+// the conv is a 3 x 2 x 2 conv on the input grid whose weights are sums of the 27 -- 12 K units per channel chunk, 0.44 of the K loop.
+// Never split (the host routes S == 1 only): the K range is the whole folded loop.
+template <bool STATS_>
+__global__ __launch_bounds__(768, 3) void k_conv_ws_fold(const es_conv_args a, const ConvGeom g) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    unsigned long long* stamp = nullptr;
+#ifdef ES_STAMP
+    stamp = g_stamp_buf ? g_stamp_buf + ((size_t)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) * 12 + wave) * 8 : nullptr;
+#endif
+    ES_STAMP_AT(0);
+    const long M = (long)g.O * g.D * g.H * g.W;
+    int bx, by, bz;
+    conv_tile_of(a, bx, by, bz);
+    conv_ws_tile<256, 8, 4, true, ES_EPI_NONE, STATS_, 3, true>(a, g, 0, smem, wave, lane, M, bx, by, 0, 12 * (a.Cin >> 5), 1, 0, stamp);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2767,6 +2828,79 @@ extern "C" int es_pack_conv_f16_dev(const float* d_w, int N, int CinW, int taps,
     return 0;
 }
 
+// ---- Folded image of an ES_CONV_UP_HW conv (k_conv_ws_fold; es_conv_args.w2) -------------------------------------------------------
+// Four class images, class = 2 ph + pw (the parity of the output voxel's h and w), each the ordinary tiled image of a 12-tap conv
+// [n-tile][K step = chunk * 12 + (kd * 4 + jh * 2 + jw)][1024 slots], concatenated.  Along H, class ph = 0 reads input rows hi - 1, hi
+// with w[kh = -1] and w[0] + w[+1]; ph = 1 reads hi, hi + 1 with w[-1] + w[0] and w[+1]; W folds the same way.  The sums are formed in
+// fp64 from the fp32 weights and rounded to f16 ONCE (through a round-to-odd fp32, so host and device agree bit for bit).
+__host__ __device__ static inline float up_fold_weight(const float* w27, int cls, int tap12) {
+    const int ph = cls >> 1, pw = cls & 1, kd = tap12 >> 2, jh = (tap12 >> 1) & 1, jw = tap12 & 1;
+    const int h0 = jh == 0 ? 0 : (ph == 0 ? 1 : 2), h1 = jh == 0 ? (ph == 0 ? 0 : 1) : 2;
+    const int w0 = jw == 0 ? 0 : (pw == 0 ? 1 : 2), w1 = jw == 0 ? (pw == 0 ? 0 : 1) : 2;
+    double s = 0.0;
+    for (int kh = h0; kh <= h1; ++kh)
+        for (int kw = w0; kw <= w1; ++kw) s += (double)w27[kd * 9 + kh * 3 + kw];
+    float f = (float)s;
+    if ((double)f != s) {                          // round to odd: the f16 rounding that follows is then the only one
+        uint32_t u = __builtin_bit_cast(uint32_t, f);
+        const double af = f < 0.f ? -(double)f : (double)f, as = s < 0.0 ? -s : s;
+        if (af > as) --u;
+        u |= 1u;
+        f = __builtin_bit_cast(float, u);
+    }
+    return f;
+}
+
+extern "C" size_t es_pack_conv_up_fold_f16_size(int N, int Cin) { return 4 * es_pack_conv_f16_size(N, Cin, 12); }
+
+// h_w: [N][CinW][27]
+extern "C" int es_pack_conv_up_fold_f16(const float* h_w, int N, int CinW, uint16_t* h_out) {
+    ES_REQUIRE(h_w && h_out && N > 0 && CinW > 0, "es_pack_conv_up_fold_f16: N=%d Cin=%d", N, CinW);
+    const int Cin = (CinW + 31) / 32 * 32;
+    const int nt = (N + BN - 1) / BN, kch = Cin / 32;
+    es_parallel_for(4L * nt * kch * 12, [=](long bi) {
+        const int tap = (int)(bi % 12), kc = (int)((bi / 12) % kch), t = (int)((bi / (12L * kch)) % nt), cls = (int)(bi / (12L * kch * nt));
+        uint16_t* blk = h_out + (size_t)bi * (BNP * BK);
+        for (int p = 0; p < BNP * 4; ++p) {
+            const int row = p >> 2, lc = (p & 3) ^ h_swz(row);
+            const int n = t * BN + row;
+            for (int e = 0; e < 8; ++e) {
+                const int c = kc * 32 + lc * 8 + e;
+                blk[p * 8 + e] = (row < BN && n < N && c < CinW) ? f32_to_f16_bits(up_fold_weight(h_w + ((size_t)n * CinW + c) * 27, cls, tap)) : 0;
+            }
+        }
+    });
+    return 0;
+}
+
+__global__ __launch_bounds__(256) void k_pack_conv_up_fold_f16(const float* __restrict__ w, int N, int CinW, int kch, int nt, h8* __restrict__ out, long nslots) {
+    const long s = (long)blockIdx.x * 256 + threadIdx.x;
+    if (s >= nslots) return;
+    const int p = (int)(s & (BNP * 4 - 1));
+    const long bi = s / (BNP * 4);
+    const int tap = (int)(bi % 12), kc = (int)((bi / 12) % kch), t = (int)((bi / (12L * kch)) % nt), cls = (int)(bi / (12L * kch * nt));
+    const int row = p >> 2, lc = (p & 3) ^ ((0x1320 >> (((row >> 2) & 3) * 4)) & 3);
+    const int n = t * BN + row;
+    h8 v;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const int c = kc * 32 + lc * 8 + e;
+        v[e] = (row < BN && n < N && c < CinW) ? (_Float16)up_fold_weight(w + ((size_t)n * CinW + c) * 27, cls, tap) : (_Float16)0.f;
+    }
+    out[s] = v;
+}
+
+// the same image (bit-identical) from an fp32 weight [N][CinW][27] already on the device
+extern "C" int es_pack_conv_up_fold_f16_dev(const float* d_w, int N, int CinW, uint16_t* d_out, es_stream stream) {
+    ES_REQUIRE(d_w && d_out && N > 0 && CinW > 0, "es_pack_conv_up_fold_f16_dev: N=%d Cin=%d", N, CinW);
+    const int Cin = (CinW + 31) / 32 * 32;
+    const long nslots = (long)es_pack_conv_up_fold_f16_size(N, Cin) / 8;
+    hipLaunchKernelGGL(k_pack_conv_up_fold_f16, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_w, N, CinW, Cin / 32,
+                       (N + BN - 1) / BN, (h8*)d_out, nslots);
+    ES_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 // Row-major image [N][taps][Cin] for k_conv_small_n (N <= 4)
 extern "C" int es_pack_conv_rows_f16(const float* h_w, int N, int CinW, int taps, uint16_t* h_out) {
     const int Cin = (CinW + 31) / 32 * 32;
@@ -2842,13 +2976,14 @@ struct LdsLimits {
 enum class ConvKernel {
     none,                      // nothing conv_launch() can launch: a chunked route, or forcing options that name a tile that is not built
     small_n, small_n_tiled, n16, kw_4_1, kw_2_2, ws_256_8_4_3, ws_64_4_4_3, ws_64_4_4_6, ws_128_4_4_3, ws_128_4_8_3, ws_128_4_8_5, ws3,
+    ws_256_up_fold,            // k_conv_ws_fold: ws_256_8_4_3 of an UP_HW launch on its folded weight image (12 K units per chunk, not 27)
     linear_ws, linear_deep, lean_256, lean_128, lean_64
 };
 // the enumerators' spelling, in their order (es_conv_kernel_of): a kernel added to the enum is added here
 static const char* const kConvKernelName[] = {
     "none",
     "small_n", "small_n_tiled", "n16", "kw_4_1", "kw_2_2", "ws_256_8_4_3", "ws_64_4_4_3", "ws_64_4_4_6", "ws_128_4_4_3", "ws_128_4_8_3", "ws_128_4_8_5", "ws3",
-    "linear_ws", "linear_deep", "lean_256", "lean_128", "lean_64"
+    "ws_256_up_fold", "linear_ws", "linear_deep", "lean_256", "lean_128", "lean_64"
 };
 static_assert(sizeof(kConvKernelName) / sizeof(kConvKernelName[0]) == (size_t)ConvKernel::lean_64 + 1, "kConvKernelName: one name per ConvKernel value");
 enum class ConvReduce { none, plain, gn_part };      // k_conv_splitk_reduce / k_conv_splitk_reduce_gn behind a launch split over workgroups
@@ -3157,6 +3292,13 @@ static int conv_route(const es_conv_args* a, ConvRoute* r) {
             static const char* a3_env = getenv("ES_CONV_A3");
             const bool a3 = (a3_env ? atoi(a3_env) != 0 : ES_CONV_A3_DEFAULT) && a->taps == 27 && a->mode == ES_CONV_SAME && !a->a2 && a->W <= 16 && a->W >= 4;
             r->kernel = a3 ? ConvKernel::ws3 : ConvKernel::ws_256_8_4_3;
+            // An UP_HW launch that carries its folded image (w2, read by no other UP launch: they have no skip phase) multiplies 12 folded
+            // taps per chunk instead of 27 (k_conv_ws_fold) -- only here: an unsplit launch of a non-sharded plan (O_hint == 0: the
+            // canonical and the sharded arithmetic stay the 27-tap one) whose 256-row tiles are each one parity class of one object.
+            // Other products than the 27-tap route's (the folded weights are rounded after the sum): not bit-equal to it.
+            if (r->kernel == ConvKernel::ws_256_8_4_3 && a->mode == ES_CONV_UP_HW && a->w2 && !a->a2 && S == 1 && a->O_hint == 0 &&
+                a->H >= 2 && a->W >= 2 && ((long)a->D * g.Hi * g.Wi) % 256 == 0)
+                r->kernel = ConvKernel::ws_256_up_fold;
         } else
             r->kernel = ConvKernel::lean_256;
     } else if ((wg128 >= 512 || S > 1) && !tiny_split) {
@@ -3242,7 +3384,8 @@ static int conv_launch(const es_conv_args* a, const ConvRoute& r, hipStream_t st
                                {(const void*)k_conv_lean<64, 4>, LDS64}, {(const void*)k_conv_lean<64, 4, true>, LDS64},
                                {(const void*)k_linear_deep, LDSDEEP},
                                {(const void*)k_linear_ws<ES_EPI_NONE>, LDSLIN}, {(const void*)k_linear_ws<ES_EPI_GEGLU>, LDSLIN},
-                               {(const void*)k_conv_ws3<false>, LDSWS3}, {(const void*)k_conv_ws3<true>, LDSWS3}};
+                               {(const void*)k_conv_ws3<false>, LDSWS3}, {(const void*)k_conv_ws3<true>, LDSWS3},
+                               {(const void*)k_conv_ws_fold<false>, LDS256}, {(const void*)k_conv_ws_fold<true>, LDS256}};
     ES_REQUIRE(lim.err == hipSuccess, "es_conv_mfma_f16: hipFuncSetAttribute failed: %s", hipGetErrorString(lim.err));
     // (the queries answer for such a route; only the launch refuses it)
     ES_REQUIRE(r.kernel != ConvKernel::none, "es_conv_mfma_f16: %s", r.omax ? "a chunked route is launched chunk by chunk" : r.unbuilt);
@@ -3268,6 +3411,10 @@ static int conv_launch(const es_conv_args* a, const ConvRoute& r, hipStream_t st
     case ConvKernel::ws3:
         if (r.stats) hipLaunchKernelGGL((k_conv_ws3<true>), r.grid, dim3(768), LDSWS3, st, *a, r.g);
         else hipLaunchKernelGGL((k_conv_ws3<false>), r.grid, dim3(768), LDSWS3, st, *a, r.g);
+        break;
+    case ConvKernel::ws_256_up_fold:
+        if (r.stats) hipLaunchKernelGGL((k_conv_ws_fold<true>), r.grid, dim3(768), LDS256, st, *a, r.g);
+        else hipLaunchKernelGGL((k_conv_ws_fold<false>), r.grid, dim3(768), LDS256, st, *a, r.g);
         break;
     case ConvKernel::linear_ws:
         if (r.geglu) hipLaunchKernelGGL((k_linear_ws<ES_EPI_GEGLU>), r.grid, dim3(768), LDSLIN, st, *a, r.g, r.ncb);

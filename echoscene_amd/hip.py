@@ -200,6 +200,9 @@ EXPORTS = {
     'es_pack_conv_f16': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'es_pack_conv_f16_dev': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'es_pack_conv_rows_f16': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'es_pack_conv_up_fold_f16_size': (C.c_size_t, [C.c_int, C.c_int]),
+    'es_pack_conv_up_fold_f16': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    'es_pack_conv_up_fold_f16_dev': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'es_groupnorm_vol': (C.c_int, [C.POINTER(GNArgs), C.c_void_p]),
     'es_layernorm_tokens': (C.c_int, [C.POINTER(LNArgs), C.c_void_p]),
     'es_attention_f16': (C.c_int, [C.POINTER(AttnArgs), C.c_void_p]),

@@ -32,10 +32,23 @@ def _gn_rg():
     return int(opts.get('gn_rg', '1')) != 0
 
 
-class PackedConv:
-    """f16 [Npad][taps][Cin32] image of a conv / linear weight + fp32 bias on the device."""
+def up_fold_weights(W):
+    """The four 3 x 2 x 2 weights of a 3x3x3 conv behind a nearest x(1, 2, 2) up-sampling, float64 [4, N, Cin, 3, 2, 2], class =
+    2 ph + pw for output parity ph = h & 1, pw = w & 1.  After the up-sampling two of the three taps along H (and along W) read the same
+    input voxel: class ph = 0 reads input rows hi - 1, hi with w[kh = -1] and w[0] + w[+1], ph = 1 reads hi, hi + 1 with
+    w[-1] + w[0] and w[+1]; W folds the same way.  What es_pack_conv_up_fold_f16 sums (and rounds to f16 once)."""
+    W = W.detach().double().cpu()
+    assert W.dim() == 5 and tuple(W.shape[2:]) == (3, 3, 3)
+    fold = [lambda t, ax: torch.stack([t.select(ax, 0), t.select(ax, 1) + t.select(ax, 2)], ax),
+            lambda t, ax: torch.stack([t.select(ax, 0) + t.select(ax, 1), t.select(ax, 2)], ax)]
+    return torch.stack([fold[pw](fold[ph](W, 3), 4) for ph in (0, 1) for pw in (0, 1)])
 
-    def __init__(self, W, b, device, geglu=False):
+
+class PackedConv:
+    """f16 [Npad][taps][Cin32] image of a conv / linear weight + fp32 bias on the device.  ``up_fold``: also the folded image of a
+    3x3x3 weight for ES_CONV_UP_HW launches (``w_fold``; es_conv_args.w2, include/echoscene_hip.h)."""
+
+    def __init__(self, W, b, device, geglu=False, up_fold=False):
         on_gpu = torch.device(device).type == 'cuda'
         W = W.detach().float().contiguous()
         W = W.to(device) if on_gpu else W.cpu()
@@ -72,6 +85,18 @@ class PackedConv:
             hip.check(L.es_pack_conv_f16(C.c_void_p(W.data_ptr()), self.N, cin, self.taps, C.c_void_p(out.data_ptr())),
                       'es_pack_conv_f16')
         self.w = out.to(device)
+        self.w_fold = None
+        if up_fold and self.taps == 27 and not (self.N <= 4 and self.Cin <= 64):
+            n = L.es_pack_conv_up_fold_f16_size(self.N, self.Cin)
+            if on_gpu:
+                with torch.cuda.device(device):
+                    self.w_fold = torch.empty(n, dtype=torch.int16, device=device)
+                    hip.check(L.es_pack_conv_up_fold_f16_dev(hip.ptr(W), self.N, cin, hip.ptr(self.w_fold), hip.current_stream()),
+                              'es_pack_conv_up_fold_f16_dev')
+            else:
+                self.w_fold = torch.empty(n, dtype=torch.int16)
+                hip.check(L.es_pack_conv_up_fold_f16(C.c_void_p(W.data_ptr()), self.N, cin, C.c_void_p(self.w_fold.data_ptr())),
+                          'es_pack_conv_up_fold_f16')
         self.b = None if b is None else own(b, device)
         self.weight_bytes = self.N * cin * self.taps * 2
         self.cin_true = cin
@@ -204,7 +229,11 @@ class UNet3DWeights:
             elif kind == 'down':
                 d['conv'] = PC(name + '.op.weight', name + '.op.bias')
             elif kind == 'up':
-                d['conv'] = PC(name + '.conv.weight', name + '.conv.bias')
+                if precision == 'fp16' and not self.concat:
+                    # nearest x2 on H, W only: the launch may multiply 12 folded taps instead of 27 (emit_unet3d_step attaches the image)
+                    d['conv'] = PackedConv(sd[name + '.conv.weight'], sd[name + '.conv.bias'], device, up_fold=True)
+                else:
+                    d['conv'] = PC(name + '.conv.weight', name + '.conv.bias')
             self.items[name] = d
         self.emb_all = PackedLinear(torch.cat(emb_w, 0), torch.cat(emb_b, 0), device)
         self.cav_all = None if self.concat else PackedLinear(torch.cat(ca_v, 0), torch.cat(ca_b, 0), device)
@@ -805,6 +834,14 @@ def emit_unet3d_step(b, w, g, x, uc_dev, temb, step, eps_out, dims=(16, 16, 16),
                 nd = (dm[0] * 2, dm[1] * 2, dm[2] * 2) if w.concat else (dm[0], dm[1] * 2, dm[2] * 2)
                 o = sbuf(O * V_(nd), state['C'])
                 state['last_op'] = b.conv(a16, d['conv'], O, nd, mode=hip.CONV_UP_DHW if w.concat else hip.CONV_UP_HW, out_f32=o)
+                wf = getattr(d['conv'], 'w_fold', None)
+                if (wf is not None and getattr(b, 'up_fold', False) and not w.concat and not b.fp32
+                        and not int(getattr(b, 'o_hint', 0) or 0)):
+                    # the folded image rides in w2 (no up-sampling conv has a skip phase); the op, its taps and its plan signature stay
+                    # as they are and the library takes the folded route where the launch is eligible (conv_route: ws_256_up_fold).
+                    # Not under o_hint: the canonical / sharded arithmetic is the 27-tap one
+                    b.ops[state['last_op']].u.conv.w2 = wf.data_ptr()
+                    b.keep.append(wf)
                 state.update(h=o, dims=nd, h16=None)
             b.tags[name] = View(state['h'])
 

@@ -307,7 +307,8 @@ class ShapeDenoiser:
     step as one hipGraph; world > 1 splits each step at the echo all-gather."""
 
     def __init__(self, df, model_params=None, ddim_steps=100, device=None, z_shape=(3, 16, 16, 16), rank=0, world=1,
-                 group=None, deterministic=False, force_exchange=False, precision='fp16', ddim_eta=0.0, sampler='ddim', weights=None):
+                 group=None, deterministic=False, force_exchange=False, precision='fp16', ddim_eta=0.0, sampler='ddim', weights=None,
+                 up_fold=True):
         """``force_exchange``: build the sharded step structure (stem plan -> code exchange -> main plan) even at world == 1 --
         the one-GPU test of the captured RCCL exchange (tests/test_hip_scene.py).
         ``precision``: 'fp16' (product: fp16 MFMA operands, fp32 accumulate) or 'fp32' -- the VALIDATION route: fp32 activations and
@@ -364,6 +365,10 @@ class ShapeDenoiser:
         # world sizes in fp32 summation order only (5e-4 relative after 4 steps, inside the 2e-2 parity budget).  At 4 objects
         # per GPU the two modes are the same arithmetic.
         self.deterministic = deterministic
+        # ``up_fold`` (default on): the two up-sampling convs of the step carry their folded weight image (plan_vol.up_fold_weights:
+        # 12 taps per parity class instead of 27) and the library multiplies through it where the launch is eligible.  False: the
+        # plan omits the image -- the 27-tap arithmetic, for A/B runs and bisecting without a rebuild.  Never with deterministic=True.
+        self.up_fold = bool(up_fold)
         self.tables = time_tables(self.w, self.temb, self.w.shape_t, self.device)
         self._plans, self.max_plans = {}, 2
         self._cur, self._use_graph = None, True                  # the state / graph switch the shard protocol below works on
@@ -419,6 +424,7 @@ class ShapeDenoiser:
         b = Builder(self.device)
         b.shard_block = block
         b.force_exchange = self.force_exchange
+        b.up_fold = self.up_fold and not self.deterministic
         if self.deterministic:
             b.o_hint = -CANON_OBJECTS   # split-K / partial-sum tiling of the reference shard -> bit-identical latents at every world size
         plms = sampler == 'plms'

@@ -333,6 +333,13 @@ typedef struct es_conv_args {
     /* optional second contraction accumulated into the same tile: the 1x1 skip_connection of a
        ResBlock whose channel count changes (out = conv2(h) + skip(x), :294-314) */
     const void* a2; const void* w2; int32_t Cin2;
+    /* w2 WITHOUT a2, mode ES_CONV_UP_HW only: NULL, or the FOLDED image of the same weight (es_pack_conv_up_fold_f16: per output
+       parity of h and w the 3x3x3 conv on the up-sampled grid is a 3x2x2 conv on the input grid whose weights are sums of the 27
+       taps -- 12 K units per channel chunk instead of 27).  `w`, `taps` = 27 and everything else stay as they are; the library
+       multiplies through the folded image on one route only (an unsplit launch on the 256-row producer/consumer tiles with
+       O_hint == 0 and D * H/2 * W/2 % 256 == 0; es_conv_kernel_of: "ws_256_up_fold") and ignores it on every other, the fp32
+       entry point included.  The folded weights are rounded to f16 after the sum, so that route is not bit-equal to the 27-tap
+       one: a caller that needs the canonical arithmetic leaves w2 NULL (ShapeDenoiser(up_fold=False), deterministic=True) */
     const float* bias;        /* [N] (sum of both biases when a2 is used) or NULL                */
     const float* rowvec;      /* [O, rowvec_ld] per-object vector broadcast over voxels (emb_layers output /
                                  cross-attention-with-one-key output), or NULL                   */
@@ -392,7 +399,7 @@ int es_conv_emits_gn_part(const es_conv_args* args);
  * bounds stated at `splitk` are the maximum).  Launches nothing. */
 int es_conv_split_of(const es_conv_args* args);
 /* host-only: writes the name of the kernel es_conv_mfma_f16(args) would launch ("lean_64", "ws_128_4_8_5", "kw_4_1", "ws3",
- * "linear_ws", ...; "chunked" for a launch over the 2 GiB descriptor limit, "none" for forcing options that name a tile that is not
+ * "ws_256_up_fold", "linear_ws", ...; "chunked" for a launch over the 2 GiB descriptor limit, "none" for forcing options that name a tile that is not
  * built) into name_out (cap bytes, always terminated) and returns the split of K over workgroups (>= 1; a chunked launch: of a full
  * chunk); -1 on invalid arguments.  For tests and tools: the answer is no part of the numerics contract.  Launches nothing. */
 int es_conv_kernel_of(const es_conv_args* args, char* name_out, int cap);
@@ -408,6 +415,14 @@ int es_pack_conv_f16(const float* h_w, int N, int Cin, int taps, uint16_t* h_out
 /* the same image (bit-identical: round to nearest even) from an fp32 weight [N][Cin][taps] already on the device */
 int es_pack_conv_f16_dev(const float* d_w, int N, int Cin, int taps, uint16_t* d_out, es_stream stream);
 int es_pack_conv_rows_f16(const float* h_w, int N, int Cin, int taps, uint16_t* h_out);
+/* the folded image of a 3x3x3 weight [N][Cin][27] for ES_CONV_UP_HW launches (es_conv_args.w2): four images of a 12-tap conv in the
+ * layout above (K step = (Cin chunk, kd, jh, jw)), one per parity class 2 (h & 1) + (w & 1) of the output voxel, concatenated.  Along H,
+ * parity 0 reads input rows h/2 - 1, h/2 with w[kh = -1] and w[0] + w[+1]; parity 1 reads h/2, h/2 + 1 with w[-1] + w[0] and w[+1]; W
+ * folds the same way.  The sums are formed in fp64 from the fp32 weights and rounded to f16 once; host and device images agree bit
+ * for bit.  The size is in f16 elements, Cin already rounded up to 32 as for es_pack_conv_f16_size. */
+size_t es_pack_conv_up_fold_f16_size(int N, int Cin);
+int es_pack_conv_up_fold_f16(const float* h_w, int N, int Cin, uint16_t* h_out);
+int es_pack_conv_up_fold_f16_dev(const float* d_w, int N, int Cin, uint16_t* d_out, es_stream stream);
 
 typedef struct es_gn_args {
     const float* x1; int32_t C1;     /* fp32 channels-last source 1 [O, V, C1]                  */

@@ -1,0 +1,56 @@
+"""Which kernels did a change touch?  Compares two device assembly listings of one source file kernel by kernel:
+
+    hipcc --offload-arch=gfx950 -O3 -std=c++17 --cuda-device-only -S es_vol.hip -o new.s      (and the same on the parent's sources)
+    python tools/kernel_asm_diff.py parent.s new.s
+
+Per `.amdhsa_kernel` symbol the text from the symbol's label to its `.Lfunc_end` (instructions and the kernel descriptor with its
+register counts), comments stripped and the function index in local labels normalised, is hashed.  Prints how many kernels are
+identical under the same symbol, names the ones that differ or went, and lists the new ones with their register and spill counts
+(profiles/conv_route_split_notes.md describes the method; profiles/up_fold_notes.md uses it).  CPU only."""
+import re, sys, hashlib, subprocess
+
+
+def kernels(path):
+    txt = open(path).read()
+    names = re.findall(r'^\s*\.amdhsa_kernel\s+(\S+)', txt, re.M)
+    out, meta = {}, {}
+    for n in names:
+        m = re.search(r'^%s:[^\n]*\n(.*?)^\.Lfunc_end(\d+):' % re.escape(n), txt, re.M | re.S)
+        body = m.group(1)
+        idx = m.group(2)
+        lines = []
+        for ln in body.split('\n'):
+            ln = ln.split(';')[0].rstrip()
+            if not ln.strip():
+                continue
+            ln = re.sub(r'\.LBB%s_' % idx, '.LBB_', ln)
+            ln = re.sub(r'\.Ltmp\d+', '.Ltmp', ln)
+            lines.append(ln)
+        out[n] = hashlib.sha1('\n'.join(lines).encode()).hexdigest()
+        k = re.search(r'\.amdhsa_kernel\s+%s\n(.*?)\.end_amdhsa_kernel' % re.escape(n), txt, re.S).group(1)
+        meta[n] = dict(vgpr=re.search(r'\.amdhsa_next_free_vgpr\s+(\d+)', k).group(1), accum=re.search(r'\.amdhsa_accum_offset\s+(\d+)', k).group(1))
+    # spills from the metadata
+    for m in re.finditer(r'\.name:\s+(\S+)\n(.*?)\.wavefront_size', txt, re.S):
+        n = m.group(1)
+        if n in meta:
+            for key in ('vgpr_count', 'vgpr_spill_count', 'sgpr_spill_count', 'private_segment_fixed_size', 'agpr_count'):
+                mm = re.search(r'\.%s:\s+(\d+)' % key, m.group(2))
+                if mm:
+                    meta[n][key] = mm.group(1)
+    return out, meta
+
+
+a, ma = kernels(sys.argv[1])
+b, mb = kernels(sys.argv[2])
+dem = lambda n: subprocess.run(['c++filt', n], capture_output=True, text=True).stdout.strip()
+same = [n for n in a if n in b and a[n] == b[n]]
+diff = [n for n in a if n in b and a[n] != b[n]]
+print('parent kernels %d, new kernels %d, identical under the same symbol %d' % (len(a), len(b), len(same)))
+for n in diff:
+    print('DIFFERS', dem(n))
+for n in a:
+    if n not in b:
+        print('GONE', dem(n))
+for n in b:
+    if n not in a:
+        print('NEW', dem(n), mb[n])
