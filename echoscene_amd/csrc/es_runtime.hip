@@ -78,6 +78,7 @@ static int dispatch(const es_op& op, hipStream_t s) {
         case ES_OP_PLMS: return es_plms_update(&op.u.plms, s);
         case ES_OP_PLMS_FIRST_A: return es_plms_first_a(&op.u.plms, s);
         case ES_OP_PLMS_FIRST_B: return es_plms_first_b(&op.u.plms, s);
+        case ES_OP_DDIM_ROWS: return es_ddim_rows_update(&op.u.keep, s);
         default: es_set_error("plan: unknown op kind %d", op.kind); return 3;
     }
 }
@@ -292,7 +293,7 @@ extern "C" int es_op_pointer_offsets(int kind, size_t* out, int cap) {
         case ES_OP_CONV_C1:
             v = {ES_PTR(conv_c1.x), ES_PTR(conv_c1.w), ES_PTR(conv_c1.bias), ES_PTR(conv_c1.out_f32), ES_PTR(conv_c1.out_f16)};
             break;
-        case ES_OP_DDPM_KEEP:
+        case ES_OP_DDPM_KEEP: case ES_OP_DDIM_ROWS:
             v = {ES_PTR(keep.x), ES_PTR(keep.eps), ES_PTR(keep.noise), ES_PTR(keep.coef), ES_PTR(keep.step), ES_PTR(keep.x0), ES_PTR(keep.mask),
                  ES_PTR(keep.keep_noise), ES_PTR(keep.tab)};
             break;
@@ -504,8 +505,9 @@ static es_model* model_load_impl(const char* path, FILE* fp, es_model* m) {
             for (const es_op& op : ops)
                 if ((op.kind == ES_OP_DDPM || op.kind == ES_OP_DDIM) && op.u.update.coef_stride > 0)
                     m->schedule_len = (long)(r.bytes / ((size_t)op.u.update.coef_stride * 4));
-                else if (op.kind == ES_OP_DDPM_KEEP && op.u.keep.coef_stride > 0) {
+                else if ((op.kind == ES_OP_DDPM_KEEP || op.kind == ES_OP_DDIM_ROWS) && op.u.keep.coef_stride > 0) {
                     // the masked loop reads tab / keep_noise by iteration too: the shorter of the two tables bounds the run
+                    // (the strided DDIM update of the layout loop carries its iteration count in n_tab, masked or not)
                     const long by_coef = (long)(r.bytes / ((size_t)op.u.keep.coef_stride * 4));
                     m->schedule_len = by_coef < op.u.keep.n_tab ? by_coef : (long)op.u.keep.n_tab;
                 }
@@ -573,7 +575,8 @@ extern "C" int es_layout_sample_keep(es_model* m, const float* noise, int noise_
     ES_REQUIRE(m && m->plan && noise && x0 && mask && keep_noise && x_out && n_steps >= 0 && noise_rows >= n_steps + 1,
                "es_layout_sample_keep: bad args (noise rows %d, steps %d)", noise_rows, n_steps);
     const es_ddpm_keep_args* k = nullptr;
-    for (const es_op& op : m->plan->ops) if (op.kind == ES_OP_DDPM_KEEP) k = &op.u.keep;
+    for (const es_op& op : m->plan->ops)
+        if (op.kind == ES_OP_DDPM_KEEP || (op.kind == ES_OP_DDIM_ROWS && op.u.keep.mask)) k = &op.u.keep;
     ES_REQUIRE(k, "es_layout_sample_keep: the model was not saved with keep=True (no masked update op)");
     ES_REQUIRE(n_steps <= k->n_tab, "es_layout_sample_keep: %d steps exceed the model's schedule (%d steps)", n_steps, k->n_tab);
     void *x = nullptr, *nz = nullptr, *rx0 = nullptr, *rmask = nullptr, *rkn = nullptr, *rtab = nullptr, *step = nullptr;

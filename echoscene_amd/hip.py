@@ -115,6 +115,7 @@ class BlendArgs(C.Structure):
                 ('tab', C.c_void_p), ('step', C.c_void_p), ('O', C.c_int32), ('n', C.c_int32)]
 
 OP_PLMS, OP_PLMS_FIRST_A, OP_PLMS_FIRST_B = 23, 24, 25     # PLMS sampling of the shape branch (csrc/es_plms.hip); 22 stays unassigned
+OP_DDIM_ROWS = 27                          # the strided DDIM update of the layout loop, masked or not (csrc/es_layout_ddim.hip; DdpmKeepArgs); 26 stays unassigned
 
 
 class PlmsArgs(C.Structure):
@@ -182,6 +183,7 @@ EXPORTS = {
     'es_ddim_blend': (C.c_int, [C.POINTER(BlendArgs), C.c_void_p]),
     'es_conv_c1_f32': (C.c_int, [C.POINTER(ConvC1Args), C.c_void_p]),
     'es_ddpm_update_keep': (C.c_int, [C.POINTER(DdpmKeepArgs), C.c_void_p]),
+    'es_ddim_rows_update': (C.c_int, [C.POINTER(DdpmKeepArgs), C.c_void_p]),
     'es_plms_update': (C.c_int, [C.POINTER(PlmsArgs), C.c_void_p]),
     'es_plms_first_a': (C.c_int, [C.POINTER(PlmsArgs), C.c_void_p]),
     'es_plms_first_b': (C.c_int, [C.POINTER(PlmsArgs), C.c_void_p]),

@@ -32,6 +32,7 @@ def _dev(module):
 
 
 _BOX_OPTS = ('keep_box_nodes', 'keep_boxes', 'keep_box_noise')
+_LAYOUT_OPTS = ('layout_sampler', 'layout_steps', 'layout_eta')
 
 
 def _hip_device(d):
@@ -69,10 +70,13 @@ class EchoToLayout(nn.Module):
         self.bbox_dim = self.translation_dim + self.size_dim + self.angle_dim
         self.trainable_params = list(self.df.parameters())
         self.scene_ids = None
-        self._den = None
+        self.layout_sampler = 'ddpm'                    # 'ddim': the reference's DDIMSampler on a strided schedule of the trained timesteps
+        self.layout_steps = None                        # ... of this many steps (needed with 'ddim')
+        self.layout_eta = 0.0
+        self._den, self._dens = None, {}
 
     def invalidate(self):
-        self._den = None
+        self._den, self._dens = None, {}
 
     def set_input(self, data_dict):
         self.preds = data_dict['preds']
@@ -82,20 +86,58 @@ class EchoToLayout(nn.Module):
     def forward(self, *a, **k):
         raise NotImplementedError('training (EchoToLayout.forward / losses) is out of scope of this build')
 
-    def _denoiser(self):
-        if self._den is None:
-            from ..samplers import LayoutDenoiser
-            self._den = LayoutDenoiser(self.df.model, self.df.diffusion_kwargs, _hip_device(_dev(self.df)))
-        return self._den
+    def layout_options(self, sampler=None, steps=None, eta=None):
+        """``layout_sampler=`` / ``layout_steps=`` / ``layout_eta=`` of the sampling calls (None: the attributes of the same names)
+        -> the validated (sampler, steps, eta).  No device work."""
+        from ..schedules import LAYOUT_SAMPLERS
+        sampler = self.layout_sampler if sampler is None else sampler
+        if sampler not in LAYOUT_SAMPLERS:
+            raise ValueError('layout_sampler must be one of %s, got %r' % (LAYOUT_SAMPLERS, sampler))
+        if sampler == 'ddpm':
+            if steps is not None or (eta is not None and float(eta) != 0.0):
+                raise ValueError("layout_steps / layout_eta need layout_sampler='ddim' (the ancestral 'ddpm' loop runs every trained timestep)")
+            return 'ddpm', None, 0.0
+        steps = self.layout_steps if steps is None else steps
+        eta = self.layout_eta if eta is None else eta
+        if steps is None or int(steps) < 1:
+            raise ValueError("layout_sampler='ddim' needs layout_steps, a positive step count; got %r" % (steps,))
+        if self.df.diffusion_kwargs.get('model_mean_type', 'eps') != 'eps':
+            raise ValueError("layout_sampler='ddim': model_mean_type=%r has no reference arithmetic under DDIM"
+                             % (self.df.diffusion_kwargs.get('model_mean_type'),))
+        return 'ddim', int(steps), float(eta)
+
+    def _denoiser(self, sampler=None, steps=None, eta=None):
+        """The default ('ddpm') denoiser lives in ``_den`` as it always has; another (sampler, steps, eta) gets a denoiser of its own -- its
+        schedule, time tables and plans -- on the SAME packed weights; the two most recent of those stay resident."""
+        sampler, steps, eta = self.layout_options(sampler, steps, eta)
+        from ..samplers import LayoutDenoiser
+        if sampler == 'ddpm':
+            if self._den is None:
+                w = next((d.w for d in self._dens.values()), None)
+                self._den = LayoutDenoiser(self.df.model, self.df.diffusion_kwargs, _hip_device(_dev(self.df)), weights=w)
+            return self._den
+        key = (sampler, steps, eta)
+        den = self._dens.get(key)
+        if den is None:
+            w = self._den.w if self._den is not None else next((d.w for d in self._dens.values()), None)
+            den = LayoutDenoiser(self.df.model, self.df.diffusion_kwargs, _hip_device(_dev(self.df)), sampler=sampler, steps=steps,
+                                 eta=eta, weights=w)
+            while len(self._dens) >= 2:
+                self._dens.pop(next(iter(self._dens)))
+            self._dens[key] = den
+        return den
 
     @torch.no_grad()
     def generate_layout_sg(self, box_dim, text=None, ret_traj=False, ddim=False, clip_denoised=False,
-                           batch_seeds=None, noise=None, x0=None, mask=None, keep_noise=None):
+                           batch_seeds=None, noise=None, x0=None, mask=None, keep_noise=None, *, layout_sampler=None,
+                           layout_steps=None, layout_eta=None):
         """echo2layout.py:112-126.  ``noise`` (optional, f32[T+1,O,box_dim]) makes the run reproducible.
         ``clip_denoised`` reaches the loop (gen_samples_sg, echo2layout.py:108; diffusion_ddpm.py:243-244).  ``ret_traj``, ``ddim``,
         ``text`` and ``batch_seeds`` are accepted and -- exactly as in the reference, whose ``sample`` (echo2layout.py:102-110)
-        passes none of them on -- have no effect.  ``x0`` / ``mask`` / ``keep_noise``: the masked loop (LayoutDenoiser.sample)."""
-        return self.split_boxes(self._denoiser().sample(self.uc_rel, self.preds, noise=noise, clip_denoised=bool(clip_denoised),
+        passes none of them on -- have no effect.  ``x0`` / ``mask`` / ``keep_noise``: the masked loop (LayoutDenoiser.sample).
+        ``layout_sampler`` / ``layout_steps`` / ``layout_eta`` (keyword-only): see layout_options; ``noise`` is then
+        f32[n_iter+1,O,box_dim] over the strided schedule's iterations."""
+        return self.split_boxes(self._denoiser(layout_sampler, layout_steps, layout_eta).sample(self.uc_rel, self.preds, noise=noise, clip_denoised=bool(clip_denoised),
                                                         x0=x0, mask=mask, keep_noise=keep_noise))
 
     def split_boxes(self, x):
@@ -409,8 +451,10 @@ class _SceneModel(nn.Module):
             x0[rows] = boxes[src].to(device).float()
         return dict(x0=x0, mask=mask.to(device), keep_noise=keep_box_noise)
 
-    def _layout(self, triples, obj_embed_, relation_cond, noise=None, *, keep_box_nodes=None, keep_boxes=None, keep_box_noise=None):
+    def _layout(self, triples, obj_embed_, relation_cond, noise=None, *, keep_box_nodes=None, keep_boxes=None, keep_box_noise=None,
+                layout_sampler=None, layout_steps=None, layout_eta=None):
         kw = self._box_keep(keep_box_nodes, keep_boxes, keep_box_noise, obj_embed_.shape[0], obj_embed_.device)
+        kw.update(layout_sampler=layout_sampler, layout_steps=layout_steps, layout_eta=layout_eta)
         self.LayoutDiff.set_input({'preds': triples, 'box': None, 'uc_b': obj_embed_, 'c_b': relation_cond,
                                    'obj_id_to_scene': None})
         return self.LayoutDiff.generate_layout_sg(box_dim=self.diff_cfg.layout_branch.denoiser_kwargs.in_channels,
@@ -478,7 +522,8 @@ class Sg2ScDiffModel(_SceneModel):
 
     def _layout_and_shapes(self, gen_shape, dec_objs, dec_triples, obj_embed_, latent, layout_noise, shape_noise, *,
                            keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None, keep_boxes=None,
-                           keep_box_noise=None, shape_sampler=None, shape_steps=None):
+                           keep_box_noise=None, shape_sampler=None, shape_steps=None, layout_sampler=None, layout_steps=None,
+                           layout_eta=None):
         """The two loops only share the setup (the reference runs them back to back, EchoScene.py:402-419).  Here they are
         ONE replayed hipGraph: each replay is a DDIM shape step with ten ancestral layout steps on a parallel branch
         (samplers.sample_layout_and_shape), then the VQ-VAE decode.
@@ -493,13 +538,21 @@ class Sg2ScDiffModel(_SceneModel):
 
         ``shape_sampler`` / ``shape_steps``: sampler ('ddim' | 'plms') and step count of the shape loop (None: ``ShapeDiff.shape_sampler`` /
         ``ShapeDiff.ddim_steps``); they combine freely with both keep families.  With ``gen_shape=False`` no shape loop runs and they
-        are not looked at (unlike ``keep_nodes``, which names inputs that would be dropped, they only choose how a loop would run)."""
+        are not looked at (unlike ``keep_nodes``, which names inputs that would be dropped, they only choose how a loop would run).
+
+        ``layout_sampler`` / ``layout_steps`` / ``layout_eta``: sampler ('ddpm' | 'ddim'), step count and eta of the LAYOUT loop (None:
+        the attributes of ``LayoutDiff``, i.e. the ancestral loop over every trained timestep); with or without gen_shape, and with
+        both keep families and the shape keywords.  Each replay of the fused graph then carries n_iter_layout // n_iter_shape layout
+        steps (samplers.sample_layout_and_shape)."""
+        lopts = dict(layout_sampler=layout_sampler, layout_steps=layout_steps, layout_eta=layout_eta)
+        self.LayoutDiff.layout_options(**{k[len('layout_'):]: v for k, v in lopts.items()})
         if (keep_nodes is None) != (keep_sdfs is None):
             raise ValueError('keep_nodes and keep_sdfs go together')
         if not gen_shape:
             if keep_nodes is not None:
                 raise ValueError('keep_nodes / keep_sdfs keep SHAPES: they need gen_shape=True')
-            return None, self._layout(dec_triples, obj_embed_, latent, layout_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise)
+            return None, self._layout(dec_triples, obj_embed_, latent, layout_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise,
+                                      **lopts)
         bk = self._box_keep(keep_box_nodes, keep_boxes, keep_box_noise, obj_embed_.shape[0], obj_embed_.device)
         from ..samplers import sample_layout_and_shape
         uc = self._rel_s(obj_embed_)
@@ -519,7 +572,7 @@ class Sg2ScDiffModel(_SceneModel):
             kw.update(x0=x0, mask=mask, keep_noise=keep_noise)
         if bk:
             kw.update(box_x0=bk['x0'], box_mask=bk['mask'], box_keep_noise=bk['keep_noise'])
-        x, z = sample_layout_and_shape(L._denoiser(), sden, obj_embed_, dec_triples, uc, c if need_c else None,
+        x, z = sample_layout_and_shape(L._denoiser(layout_sampler, layout_steps, layout_eta), sden, obj_embed_, dec_triples, uc, c if need_c else None,
                                        layout_noise=layout_noise, shape_noise=shape_noise, **kw)
         boxes = L.split_boxes(x)
         S.gen_z = z
@@ -542,14 +595,16 @@ class Sg2ScDiffModel(_SceneModel):
     @torch.no_grad()
     def sample(self, dec_objs, dec_triplets, dec_text_feat, dec_rel_feat, gen_shape=False, layout_noise=None,
                shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None,
-               keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None):
+               keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None, layout_sampler=None,
+               layout_steps=None, layout_eta=None):
         """EchoScene.py:388-420.  ``keep_nodes`` / ``keep_sdfs`` and ``keep_box_nodes`` / ``keep_boxes`` (keyword-only): see
         _layout_and_shapes."""
         oe, _, latent_m = self._setup(dec_objs, dec_triplets, dec_text_feat, dec_rel_feat,
                                       dec_objs, dec_triplets, dec_text_feat, dec_rel_feat)
         sdf, boxes = self._layout_and_shapes(gen_shape, dec_objs, dec_triplets, oe, latent_m, layout_noise, shape_noise,
                                              keep_nodes=keep_nodes, keep_sdfs=keep_sdfs, keep_noise=keep_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise,
-                                             shape_sampler=shape_sampler, shape_steps=shape_steps)
+                                             shape_sampler=shape_sampler, shape_steps=shape_steps,
+                            layout_sampler=layout_sampler, layout_steps=layout_steps, layout_eta=layout_eta)
         return {'shapes': sdf}, boxes
 
     def _edited(self, enc, dec, touched, added, gen_shape, layout_noise, shape_noise, change_rows=None, strict=False, **opts):
@@ -564,19 +619,22 @@ class Sg2ScDiffModel(_SceneModel):
     def sample_with_changes(self, enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triplets,
                             dec_text_feat, dec_rel_feat, manipulated_nodes, gen_shape=False, layout_noise=None,
                             shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None,
-                            keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None):
+                            keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None, layout_sampler=None,
+               layout_steps=None, layout_eta=None):
         """EchoScene.py:422-472.  ``keep_nodes`` / ``keep_sdfs`` (keyword-only): see _layout_and_shapes."""
         return self._edited((enc_objs, enc_triples, enc_text_feat, enc_rel_feat),
                             (dec_objs, dec_triplets, dec_text_feat, dec_rel_feat),
                             list(manipulated_nodes), [], gen_shape, layout_noise, shape_noise,
                             keep_nodes=keep_nodes, keep_sdfs=keep_sdfs, keep_noise=keep_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise,
-                            shape_sampler=shape_sampler, shape_steps=shape_steps)
+                            shape_sampler=shape_sampler, shape_steps=shape_steps,
+                            layout_sampler=layout_sampler, layout_steps=layout_steps, layout_eta=layout_eta)
 
     @torch.no_grad()
     def sample_with_additions(self, enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triplets,
                               dec_text_feat, dec_rel_feat, missing_nodes, gen_shape=False, layout_noise=None,
                               shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None,
-                              keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None):
+                              keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None, layout_sampler=None,
+               layout_steps=None, layout_eta=None):
         """EchoScene.py:474-532: zero rows inserted at ``missing_nodes[i] + i``; note the reference draws the
         change noise for rows listed in ``missing_nodes`` (:489-494) but splices / masks ``nodes_added``."""
         added = [m + i for i, m in enumerate(missing_nodes)]
@@ -584,7 +642,8 @@ class Sg2ScDiffModel(_SceneModel):
                             (dec_objs, dec_triplets, dec_text_feat, dec_rel_feat),
                             added, added, gen_shape, layout_noise, shape_noise, change_rows=list(missing_nodes), strict=True,
                             keep_nodes=keep_nodes, keep_sdfs=keep_sdfs, keep_noise=keep_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise,
-                            shape_sampler=shape_sampler, shape_steps=shape_steps)
+                            shape_sampler=shape_sampler, shape_steps=shape_steps,
+                            layout_sampler=layout_sampler, layout_steps=layout_steps, layout_eta=layout_eta)
 
     def state_dict(self, epoch=None, counter=None, **kw):
         """EchoScene.py:534-543 when called with (epoch, counter); plain nn.Module.state_dict otherwise."""
@@ -607,17 +666,21 @@ class Sg2BoxDiffModel(_SceneModel):
     # EchoLayout's manipulator uses pred_embeddings_man_dc (EchoLayout.py:154), EchoScene pred_embeddings_ec
     @torch.no_grad()
     def sampleBoxes(self, dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat, layout_noise=None, *,
-                    keep_box_nodes=None, keep_boxes=None, keep_box_noise=None):
+                    keep_box_nodes=None, keep_boxes=None, keep_box_noise=None, layout_sampler=None, layout_steps=None, layout_eta=None):
         """EchoLayout.py:291-307.  ``keep_box_nodes`` / ``keep_boxes`` (keyword-only): those nodes keep the given normalised boxes
-        (_SceneModel._box_keep); also on the two editing calls."""
+        (_SceneModel._box_keep); also on the two editing calls.  ``layout_sampler`` / ``layout_steps`` / ``layout_eta`` (keyword-only):
+        sampler, step count and eta of the layout loop (EchoToLayout.layout_options); also on the two editing calls."""
+        self.LayoutDiff.layout_options(layout_sampler, layout_steps, layout_eta)
         oe, _, latent_m = self._setup(dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat,
                                       dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat,
                                       manip_pred_table='pred_embeddings_man_dc')
-        return self._layout(dec_triplets, oe, latent_m, layout_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise)
+        return self._layout(dec_triplets, oe, latent_m, layout_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise,
+                            layout_sampler=layout_sampler, layout_steps=layout_steps, layout_eta=layout_eta)
 
     def _edited(self, enc, dec, touched, added, layout_noise, keep_list=False, **box_opts):     # (keep_list: the additions call)
         """the two editing calls: the ``touched`` nodes get the change noise (sic for additions: nodes_added here, EchoLayout.py:367-372;
         EchoScene draws it for missing_nodes), take the manipulator's latent rows and are 0 in the returned keep vector"""
+        self.LayoutDiff.layout_options(*(box_opts.get(k) for k in _LAYOUT_OPTS))
         oe, latent, latent_m = self._setup(*enc, *dec, change_rows=touched, added_rows=added, manip_pred_table='pred_embeddings_man_dc')
         boxes = self._layout(dec[1], oe, self._splice(latent, latent_m, touched, strict=keep_list), layout_noise, **box_opts)
         return self._keep_vector(len(boxes['translations']), touched, None if keep_list else oe.device), boxes
@@ -625,18 +688,20 @@ class Sg2BoxDiffModel(_SceneModel):
     @torch.no_grad()
     def sampleBoxes_with_changes(self, enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triples,
                                  dec_text_feat, dec_rel_feat, manipulated_nodes, layout_noise=None, *, keep_box_nodes=None,
-                                 keep_boxes=None, keep_box_noise=None):
+                                 keep_boxes=None, keep_box_noise=None, layout_sampler=None, layout_steps=None, layout_eta=None):
         # keep: f32 [O,1] tensor on the model's device (EchoLayout.py:342-348); only the _with_additions variant returns a list
         return self._edited((enc_objs, enc_triples, enc_text_feat, enc_rel_feat), (dec_objs, dec_triples, dec_text_feat, dec_rel_feat),
-                            list(manipulated_nodes), [], layout_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise)
+                            list(manipulated_nodes), [], layout_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise,
+                            layout_sampler=layout_sampler, layout_steps=layout_steps, layout_eta=layout_eta)
 
     @torch.no_grad()
     def sampleBoxes_with_additions(self, enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triples,
                                    dec_text_feat, dec_rel_feat, missing_nodes, layout_noise=None, *, keep_box_nodes=None,
-                                   keep_boxes=None, keep_box_noise=None):
+                                   keep_boxes=None, keep_box_noise=None, layout_sampler=None, layout_steps=None, layout_eta=None):
         added = [m + i for i, m in enumerate(missing_nodes)]
         return self._edited((enc_objs, enc_triples, enc_text_feat, enc_rel_feat), (dec_objs, dec_triples, dec_text_feat, dec_rel_feat),
-                            added, added, layout_noise, keep_list=True, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise)
+                            added, added, layout_noise, keep_list=True, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise,
+                            layout_sampler=layout_sampler, layout_steps=layout_steps, layout_eta=layout_eta)
 
     def state_dict(self, epoch=None, counter=None, **kw):
         sd = super().state_dict(**kw)
@@ -708,10 +773,12 @@ class SGDiff(nn.Module):
             raise ValueError("keep_nodes / keep_sdfs keep SHAPES; an 'echolayout' model has no shape branch")
         if self.type_ == 'echolayout' and any(kw.get(k) is not None for k in ('shape_sampler', 'shape_steps')):
             raise ValueError("shape_sampler / shape_steps choose the sampler of the SHAPE loop; an 'echolayout' model has no shape branch")
+        # the layout keywords are checked before any device work (an unknown sampler, layout_steps / layout_eta without 'ddim', ...)
+        self.diff.LayoutDiff.layout_options(*(kw.get(k) for k in _LAYOUT_OPTS))
 
     @staticmethod
     def _box_kw(kw):
-        return {k: kw.get(k) for k in _BOX_OPTS}
+        return {k: kw.get(k) for k in _BOX_OPTS + _LAYOUT_OPTS}
 
     def sample_box_and_shape(self, dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat, gen_shape=False,
                              **noise):
@@ -727,7 +794,14 @@ class SGDiff(nn.Module):
         ``shape_sampler`` ('ddim' | 'plms') + ``shape_steps`` (keyword-only; None: ``diff.ShapeDiff.shape_sampler`` / ``.ddim_steps``, i.e.
         DDIM with 100 steps): sampler and step count of the shape loop.  'plms' is the reference's PLMSSampler (pseudo linear multistep,
         S + 1 denoiser evaluations for S steps; eta = 0 and at least two timesteps, else ValueError); it combines with both keep
-        families.  Also on the two editing calls.  With ``gen_shape=False`` there is no shape loop and they have no effect."""
+        families.  Also on the two editing calls.  With ``gen_shape=False`` there is no shape loop and they have no effect.
+        ``layout_sampler`` ('ddpm' | 'ddim') + ``layout_steps`` + ``layout_eta`` (keyword-only; both model types, with or without
+        gen_shape; None: ``diff.LayoutDiff.layout_sampler`` / ``.layout_steps`` / ``.layout_eta``, i.e. the ancestral loop over every
+        trained timestep): 'ddim' runs the reference's DDIMSampler on the layout denoiser over a strided schedule of ``layout_steps`` of
+        the trained timesteps (eta 0: deterministic; eta scales the per-step noise), e.g. ``layout_steps=100`` -- a tenth of the
+        launches of the layout loop.  ``layout_noise`` is then f32 [n_iter + 1, O, 8] and ``keep_box_noise`` f32 [n_iter, O, 8] over the
+        schedule's iterations.  ``layout_steps`` / ``layout_eta`` with 'ddpm', or an unknown name, is a ValueError.  They combine with
+        ``keep_box_nodes`` / ``keep_boxes`` and with the shape keywords; also on the two editing calls."""
         self._no_keep_without_shapes(noise)
         if self.type_ == 'echolayout':
             return self.diff.sampleBoxes(dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat,

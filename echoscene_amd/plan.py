@@ -584,6 +584,40 @@ class Builder:
         self.ops.append(op)
         self.keep += [x0, mask, keep_noise, tab]
 
+    def ddim_rows(self, x, eps, coef, step, noise=None, noise_stride=0, x0=None, mask=None, keep_noise=None, tab=None, inc_step=True):
+        """the strided DDIM update of the layout loop as one launch (es_ddim_rows_update): ``update(OP_DDIM, ...)`` on the rows whose mask
+        is 0 -- every row without a mask -- and what ``update_keep`` leaves in the others.  x [O, row]; coef [S, 5] (LayoutDdimSchedule);
+        ``noise`` (a View of the per-iteration draws) only when eta != 0; x0 / mask / keep_noise [S, O * row] / tab [S, 2] together or
+        not at all"""
+        a = DdpmKeepArgs()
+        if isinstance(eps, View):
+            assert eps.ld == eps.width and eps.col == 0
+            a.x, a.eps, a.eps_nslab, a.eps_slab_stride = x.data_ptr(), eps.ptr, eps.nslab, eps.slab_stride
+            self.keep.append(eps.t)
+        else:
+            a.x, a.eps = x.data_ptr(), eps.data_ptr()
+        a.noise, a.noise_stride = (noise.ptr if noise is not None else None), noise_stride
+        a.coef, a.coef_stride = coef.data_ptr(), coef.shape[1]
+        a.step = step.data_ptr()
+        a.n = x.numel()
+        a.inc_step = 1 if inc_step else 0
+        a.clip_x0 = 0
+        a.n_tab = coef.shape[0]
+        a.row = x.numel() // x.shape[0]
+        given = [t is not None for t in (x0, mask, keep_noise, tab)]
+        assert all(given) or not any(given)
+        if mask is not None:
+            a.x0, a.mask, a.keep_noise = x0.data_ptr(), mask.data_ptr(), keep_noise.data_ptr()
+            a.keep_noise_stride = keep_noise.shape[1]
+            a.tab = tab.data_ptr()
+            assert mask.numel() == x.shape[0] and x0.numel() == x.numel() and keep_noise.shape[0] >= coef.shape[0] and tab.shape[0] == coef.shape[0]
+            self.keep += [x0, mask, keep_noise, tab]
+        op = Op()
+        op.kind, op.lane = hip.OP_DDIM_ROWS, 0
+        op.u.keep = a
+        self.ops.append(op)
+        self.keep.append(coef)
+
     def rowsel(self, table, step, out, rows=1):
         """out[r, :n] = table[*step, :n] for r < rows (out: View; table: 2-D tensor [n_steps, n])"""
         a = RowSelArgs()
@@ -623,8 +657,8 @@ def count_launches(ops):
             n += 1
         if op.kind in (hip.OP_DDPM, hip.OP_DDIM) and op.u.update.inc_step and not (op.kind == hip.OP_DDPM and op.u.update.n <= 4096):
             n += 1                           # (the one-workgroup DDPM update advances the step counter itself)
-        if op.kind == hip.OP_DDPM_KEEP and op.u.keep.inc_step and op.u.keep.n > 4096:
-            n += 1                           # (es_ddpm_update_keep: as OP_DDPM)
+        if op.kind in (hip.OP_DDPM_KEEP, hip.OP_DDIM_ROWS) and op.u.keep.inc_step and op.u.keep.n > 4096:
+            n += 1                           # (es_ddpm_update_keep, es_ddim_rows_update: as OP_DDPM)
         if (op.kind == hip.OP_PLMS and op.u.plms.inc_step) or op.kind == hip.OP_PLMS_FIRST_A:
             n += 1                           # (the PLMS update's step increment; first-a sets the counter to 1)
         i += k

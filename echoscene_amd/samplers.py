@@ -9,7 +9,7 @@ import torch
 from . import hip
 from .plan import (Builder, GraphIndex, View, GCNWeights, UNet1DWeights, emit_gcn, emit_unet1d_step, time_tables, sub_plan)
 from .plan_vol import UNet3DWeights, emit_unet3d_step, VQWeights, emit_vq_decode, VQEncWeights, emit_vq_encode
-from .schedules import LayoutSchedule, ShapeSchedule, timestep_embedding_table, SHAPE_SAMPLERS
+from .schedules import LayoutSchedule, LayoutDdimSchedule, ShapeSchedule, timestep_embedding_table, SHAPE_SAMPLERS, LAYOUT_SAMPLERS
 
 
 def _cap(n_triples):
@@ -63,11 +63,19 @@ def new_state(**kw):
     return st
 
 
-def emit_layout_step(b, w, g, obj_embed, temb, tables, T, coef=None, keep_tab=None, clip=False, keep=False, eps_out=None):
+def emit_layout_step(b, w, g, obj_embed, temb, tables, T, coef=None, keep_tab=None, clip=False, keep=False, eps_out=None,
+                     sampler='ddpm', step_noise=True):
     """The layout loop step on ``b``: one UNet1D evaluation on x [O, 8] at the iteration ``step`` counts, then -- with the schedule's
     ``coef`` table -- the ancestral update (``keep``: es_ddpm_update_keep, which also carries the kept rows; it reads ``keep_tab``).
-    ``clip``: clip_denoised of the update.  ``coef=None``: the denoiser alone; ``eps_out``: a plain eps tensor instead of the output
-    conv's K slices.  Buffers are allocated in a fixed order; returns them by name (``n_eps_ops``: the ops in front of the update)."""
+    ``T``: the iterations of the loop (rows of the noise and keep tables).  ``clip``: clip_denoised of the update.  ``coef=None``: the
+    denoiser alone; ``eps_out``: a plain eps tensor instead of the output conv's K slices.
+    ``sampler='ddim'``: the same ops with the LAST one replaced by the strided DDIM update (es_ddim_rows_update, masked or not; ``coef``
+    = LayoutDdimSchedule.coef); it reads the per-iteration draws only with ``step_noise`` (eta != 0).
+    Buffers are allocated in a fixed order; returns them by name (``n_eps_ops``: the ops in front of the update)."""
+    if sampler not in LAYOUT_SAMPLERS:
+        raise ValueError('sampler must be one of %s, got %r' % (LAYOUT_SAMPLERS, sampler))
+    if sampler == 'ddim' and clip:
+        raise ValueError('layout DDIM: clip_denoised=True has no reference arithmetic under DDIM (p_sample_ddim never clips)')
     O, D = g.O, w.in_ch
     x = b.buf(O, D)
     step = b.buf(1, dtype=torch.int32, zero=True)
@@ -81,6 +89,10 @@ def emit_layout_step(b, w, g, obj_embed, temb, tables, T, coef=None, keep_tab=No
     draws = View(noise[1:].reshape(T, O * D), ld=O * D)
     if keep:
         out.update(x0=b.buf(O, D, zero=True), mask=b.buf(O, zero=True), knoise=b.buf(T, O * D, zero=True))
+    if sampler == 'ddim':
+        kw = dict(x0=out['x0'], mask=out['mask'], keep_noise=out['knoise'], tab=keep_tab) if keep else {}
+        b.ddim_rows(x, eps, coef, step, noise=draws if step_noise else None, noise_stride=O * D if step_noise else 0, inc_step=True, **kw)
+    elif keep:
         b.update_keep(x, eps, coef, step, draws, O * D, out['x0'], out['mask'], out['knoise'], keep_tab, inc_step=True, clip_x0=clip)
     else:
         b.update(hip.OP_DDPM, x, eps, coef, step, noise=draws, noise_stride=O * D, inc_step=True, clip_x0=clip)
@@ -163,16 +175,33 @@ def _check_mask(x0, mask, shape, loop, form, unit):
 class LayoutDenoiser:
     """UNet1DModel + GaussianDiffusion sampling on the HIP path (loop A of SURVEY.md section 3.1)."""
 
-    def __init__(self, net, diffusion_kwargs, device=None):
+    def __init__(self, net, diffusion_kwargs, device=None, sampler='ddpm', steps=None, eta=0.0, weights=None):
+        """``sampler``: 'ddpm' (the shipped ancestral loop over all T trained timesteps) or 'ddim' -- the reference's model-agnostic
+        DDIMSampler (samplers/ddim.py) on a strided schedule of ``steps`` of them (schedules.LayoutDdimSchedule), ``eta`` scaling its
+        per-step noise (0: deterministic).  A DDIM denoiser has its own, S-row, time-embedding table and ``time_tables``.
+        ``weights``: the packed UNet1DWeights of another LayoutDenoiser of the same network and device (another sampler or step count
+        does not need a second copy of them)."""
+        if sampler not in LAYOUT_SAMPLERS:
+            raise ValueError('layout_sampler must be one of %s, got %r' % (LAYOUT_SAMPLERS, sampler))
+        if sampler == 'ddpm' and (steps is not None or float(eta or 0.0) != 0.0):
+            raise ValueError("layout_steps / layout_eta need layout_sampler='ddim' (the ancestral loop runs every trained timestep)")
+        if sampler == 'ddim' and steps is None:
+            raise ValueError("layout_sampler='ddim' needs layout_steps")
+        self.sampler, self.eta = sampler, float(eta or 0.0)
         self.device = device or torch.device('cuda')
         self.net = net
-        self.w = UNet1DWeights(state_dict_for(net, self.device), net, self.device)
         dk = dict(diffusion_kwargs)
+        if sampler == 'ddim' and dk.get('model_mean_type', 'eps') != 'eps':
+            raise ValueError("layout DDIM: model_mean_type=%r has no reference arithmetic under DDIM" % (dk.get('model_mean_type'),))
+        self.w = weights if weights is not None else UNet1DWeights(state_dict_for(net, self.device), net, self.device)
         # every parameterisation GaussianDiffusion can sample with is a coefficient table of the same update op (schedules.py)
         self.sched = LayoutSchedule(dk.get('time_num', 1000), dk.get('beta_start', 1e-4), dk.get('beta_end', 0.02),
                                     dk.get('schedule_type', 'linear'), dk.get('model_mean_type', 'eps'),
                                     dk.get('model_var_type', 'fixedsmall'))
-        self.T = self.sched.time_num
+        self.T = self.sched.time_num                                # the model's trained timestep count
+        if sampler == 'ddim':
+            self.sched = LayoutDdimSchedule(self.sched, steps, self.eta)
+        self.n_iter = len(self.sched.timesteps)                     # iterations of the loop (T for the ancestral loop)
         self.temb = timestep_embedding_table(self.sched.timesteps, net.model_channels).to(self.device)
         self.coef = self.sched.coef.to(self.device)
         self.keep_tab = self.sched.keep_tab.to(self.device)      # masked loop: q_sample's factors per iteration (es_ddpm_update_keep)
@@ -197,7 +226,8 @@ class LayoutDenoiser:
         if st is None:
             g = GraphIndex(triples, O, self.device, capacity=cap)
             b = Builder(self.device)
-            bufs = emit_layout_step(b, self.w, g, obj_embed, self.temb, self.tables, self.T, self.coef, self.keep_tab, clip, keep)
+            bufs = emit_layout_step(b, self.w, g, obj_embed, self.temb, self.tables, self.n_iter, self.coef, self.keep_tab, clip, keep,
+                                    sampler=self.sampler, step_noise=self.sampler == 'ddpm' or self.eta != 0.0)
             n_eps_ops = bufs.pop('n_eps_ops')
             # 'eps_plan': the same ops minus the update, for step-level parity tests
             st = new_state(plan=b.finish(), eps_plan=sub_plan(b, b.ops[:n_eps_ops]), g=g, sig=sig, **bufs)
@@ -222,6 +252,8 @@ class LayoutDenoiser:
         [T, O * 8] and "ktab" [T, 2]."""
         from .plan import save_model
         st = self._plan_for(obj_embed, triples, keep=keep)
+        # (a 'ddim' denoiser's plan ends in es_ddim_rows_update: es_layout_sample / es_layout_sample_keep replay it the same way,
+        #  with n_iter for T)
         regions = dict(x=st['x'], noise=st['noise'], step=st['step'], coef=self.coef)
         if keep:
             regions.update(x0=st['x0'], mask=st['mask'], knoise=st['knoise'], ktab=self.keep_tab)
@@ -239,17 +271,18 @@ class LayoutDenoiser:
         """inputs of the masked loop into the plan's buffers (validation as ShapeDenoiser._fill_keep)"""
         O, D = st['x'].shape
         x0, mask = _check_mask(x0, mask, (O, D), 'masked layout loop', '[O, %d]' % D, 'node')
-        if keep_noise is not None and (keep_noise.dim() < 2 or keep_noise.shape[0] < self.T or keep_noise[0].numel() != O * D):
-            raise ValueError('masked layout loop: keep_noise must be [T, O, %d] with T = %d' % (D, self.T))
+        n = self.n_iter
+        if keep_noise is not None and (keep_noise.dim() < 2 or keep_noise.shape[0] < n or keep_noise[0].numel() != O * D):
+            raise ValueError('masked layout loop: keep_noise must be [T, O, %d] with T = %d' % (D, n))
         st['x0'].copy_(x0.to(self.device).float())
         st['mask'].copy_(mask.to(self.device))
         if keep_noise is None:
             st['knoise'].normal_()
         else:
-            st['knoise'].copy_(keep_noise.to(self.device).float()[:self.T].reshape(self.T, O * D))
+            st['knoise'].copy_(keep_noise.to(self.device).float()[:n].reshape(n, O * D))
 
     def _prime_keep(self, st):
-        """kept rows of x_T <- q_sample(x0, t of iteration 0, keep_noise[0]): the one launch in front of the masked loop
+        """kept rows of x_T <- q_sample(x0, t of iteration 0 -- of this denoiser's schedule --, keep_noise[0]): the one launch in front of the masked loop
         (es_ddim_blend does exactly this arithmetic at n = 8); every later q_sample is written by the step's update launch"""
         O, D = st['x'].shape
         a = hip.BlendArgs()
@@ -262,7 +295,7 @@ class LayoutDenoiser:
     def stage(self, obj_embed, triples, noise=None, x0=None, mask=None, keep_noise=None, clip=False, prime=True):
         """One call's inputs into its plan state, which is returned ready to run.  The device draws happen in THIS order (a contract:
         a caller who seeds the generator gets the same bits from the same draws made by hand): the keep table [T, O * 8], then
-        ``noise`` [T + 1, O, 8].  ``prime``: the launch that forward-noises the kept rows of x_T (not for a run of no steps)."""
+        ``noise`` [T + 1, O, 8] (T = ``n_iter``: the schedule's length under 'ddim', whatever eta is).  ``prime``: the launch that forward-noises the kept rows of x_T (not for a run of no steps)."""
         _check_keep_pair(x0, mask, keep_noise, 'the masked layout loop')
         st = self._plan_for(obj_embed, triples, clip=clip, keep=mask is not None)
         if mask is not None:
@@ -289,8 +322,17 @@ class LayoutDenoiser:
         reference defines the masked loop for shapes only, samplers/ddim.py:160-163); they take part in the step's message passing
         like every other node; after the last iteration they are ``x0`` bit for bit.  A run stopped early (``n_steps`` < T) leaves
         them at the NEXT timestep's forward-noised value.  ``clip_denoised`` never touches kept rows.  ``mask=None``: the loop and
-        its plan are what they are without this feature."""
-        n_steps = self.T if n_steps is None else n_steps
+        its plan are what they are without this feature.
+
+        A ``sampler='ddim'`` denoiser runs DDIMSampler.ddim_sampling on its strided schedule instead: T above reads ``n_iter`` (the
+        schedule's length), iteration i is at timestep ``sched.timesteps[i]``, row 1 + i of ``noise`` is the randn draw that sigma_i
+        scales (read only when eta != 0; the table keeps its [n_iter + 1, O, 8] form either way), the masked loop blends with
+        q_sample at those timesteps, and ``clip_denoised=True`` is refused."""
+        if self.sampler == 'ddim' and clip_denoised:
+            raise ValueError('layout DDIM: clip_denoised=True has no reference arithmetic under DDIM (p_sample_ddim never clips)')
+        n_steps = self.n_iter if n_steps is None else n_steps
+        if not 0 <= n_steps <= self.n_iter:
+            raise ValueError('n_steps must be in [0, %d] (the iterations of the schedule), got %r' % (self.n_iter, n_steps))
         st = self.stage(obj_embed, triples, noise, x0, mask, keep_noise, clip=bool(clip_denoised), prime=n_steps > 0)
         st['plan'].sample(st['step'], 0, n_steps, use_graph=use_graph)
         return st['x'].clone()
@@ -700,13 +742,24 @@ def keep_selection(keep_nodes, n_objects):
     return mask, rows, [first[t] for t in rows]
 
 
+def fused_iterations(n_iter_layout, n_iter_shape, first=0):
+    """Iteration arithmetic of the fused call: (r, left) = the layout steps on the parallel branch of every fused replay and the layout
+    steps that run afterwards.  The fused graph replays for the shape iterations ``first`` .. S-1 (``first`` = 1 under PLMS, whose
+    iteration 0 runs unfused); r = 0 (fewer layout than shape iterations): nothing is fused and the whole layout loop is left."""
+    r = int(n_iter_layout) // int(n_iter_shape)
+    done = r * (int(n_iter_shape) - int(first)) if r >= 1 else 0
+    return r, int(n_iter_layout) - done
+
+
 def sample_layout_and_shape(lay, shp, obj_embed, triples, uc, c=None, layout_noise=None, shape_noise=None, use_graph=True,
                             x0=None, mask=None, keep_noise=None, box_x0=None, box_mask=None, box_keep_noise=None, shape_sampler=None):
     """Both sampling loops of one scene (EchoScene.py:402-419 runs them back to back) as ONE replayed hipGraph: every replay = one
-    DDIM shape step on the main branch and ``T_layout // S_shape`` (= 10) ancestral layout steps on a parallel branch
-    (plan.combine_plans), so the latency-bound layout chain -- 131 launches of 32 workgroups per step -- runs inside the gaps
-    of the MFMA-bound shape step instead of after it (measured on the bench: 24.3 -> 23.0 ms per full step, i.e. the layout
-    step disappears).  Left-over layout steps (T not a multiple of S) run afterwards.  Returns (boxes x_0 [O, 8], latents z_0).
+    shape step on the main branch and ``r = n_iter_layout // n_iter_shape`` (= 10 by default) layout steps on a parallel branch
+    (plan.combine_plans).  The parallel branch does NOT hide the latency-bound layout chain: measured end to end
+    (profiles/r06_e2e_latency.txt) a scene call costs the plain sum of its two loops, the 1000-step layout loop 0.65 s of it at
+    any scene size -- which is why a shorter layout loop (``LayoutDenoiser(sampler='ddim', steps=...)``) shortens the call.
+    Left-over layout steps (n_iter_layout not a multiple of the shape iterations) run afterwards; r = 0 (fewer layout than shape
+    iterations) runs the two loops unfused.  Returns (boxes x_0 [O, 8], latents z_0).
     ``x0`` / ``mask`` / ``keep_noise``: the masked shape loop (ShapeDenoiser.sample).  ``box_x0`` / ``box_mask`` / ``box_keep_noise``:
     the masked layout loop (LayoutDenoiser.sample) -- its keep plan is then the side branch of the fused graph and runs the left-over
     steps; the two families are independent of each other.
@@ -723,7 +776,7 @@ def sample_layout_and_shape(lay, shp, obj_embed, triples, uc, c=None, layout_noi
     st = lay.stage(obj_embed, triples, layout_noise, box_x0, box_mask, box_keep_noise)
     ss = shp.stage(uc, triples, c, shape_noise, None, x0, mask, keep_noise, shape_sampler)
     first = 1 if ss['sampler'] == 'plms' else 0                 # PLMS: iteration 0 is not a replay of the steady step
-    r = lay.T // shp.S
+    r, _ = fused_iterations(lay.n_iter, shp.S, first)
     done = 0
     if r >= 1 and use_graph:
         fused = shp.fused_plan(st['plan'], ss, r)
@@ -734,8 +787,8 @@ def sample_layout_and_shape(lay, shp, obj_embed, triples, uc, c=None, layout_noi
         done = r * (shp.S - first)
     else:
         shp._run_loop(ss, shp.S, use_graph)
-    if done < lay.T:
-        st['plan'].sample(st['step'], done, lay.T - done, use_graph=use_graph)
+    if done < lay.n_iter:
+        st['plan'].sample(st['step'], done, lay.n_iter - done, use_graph=use_graph)
     return st['x'].clone(), ss['x'].clone()
 
 

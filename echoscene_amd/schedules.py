@@ -63,6 +63,7 @@ class LayoutSchedule:
         if model_var_type not in ('fixedsmall', 'fixedlarge'):
             raise NotImplementedError(model_var_type)
         self.time_num = time_num
+        self.model_mean_type, self.model_var_type = model_mean_type, model_var_type
         betas64 = layout_betas(schedule_type, beta_start, beta_end, time_num)
         assert (betas64 > 0).all() and (betas64 <= 1).all()                  # diffusion_ddpm.py:134
         alphas64 = 1.0 - betas64
@@ -96,37 +97,53 @@ class LayoutSchedule:
         self.sqrt_one_minus_alphas_cumprod = torch.sqrt(1.0 - ac).float()
         tsi = torch.from_numpy(self.timesteps.copy())
         self.keep_tab = torch.stack([self.sqrt_alphas_cumprod[tsi], self.sqrt_one_minus_alphas_cumprod[tsi]], dim=1).contiguous()   # [T, 2] by iteration
+        self.alphas_cumprod = ac                                            # fp32, by t: what a strided sampler reads (LayoutDdimSchedule)
+
+
+def ddim_tables(ac, steps, eta=0.0, sqrt_1m=torch.sqrt):
+    """The strided DDIM schedule over a model's fp32 ``alphas_cumprod`` [T], the ONE restatement of ``DDIMSampler.make_schedule``
+    (samplers/ddim.py:28-57), ``make_ddim_timesteps('uniform')`` / ``make_ddim_sampling_parameters`` (ldm_diffusion_util.py:68-96) and the
+    per-step numbers of ``p_sample_ddim`` (samplers/ddim.py:246-257), shared by the shape and the layout loop.  sigma_t as the reference
+    derives it: float64 arithmetic on the fp32 alphas, ``1 - alphas`` and its reciprocal formed in fp32 first, the result cast to fp32
+    when it is used; sqrt(1 - a_prev - sigma_t^2) in fp32.  Returns a dict by SCHEDULE index (ascending timesteps): ``ts`` (numpy),
+    ``a``, ``a_prev``, ``sqrt_one_minus_a``, ``sigmas`` and ``cols`` = [sqrt(1-a), sqrt(a), sqrt(a_prev), sqrt(1-a_prev-sigma^2), sigma].
+    The iteration count is len(ts), not necessarily ``steps``.
+    ``sqrt_1m``: the square root behind ``ddim_sqrt_one_minus_alphas``.  The reference takes it with numpy (``np.sqrt(1. - ddim_alphas)``,
+    samplers/ddim.py:53), which is correctly rounded; torch.sqrt on fp32 may differ from it in the last bit where the build routes it
+    through a vector math library.  ShapeSchedule has always used torch.sqrt and keeps it (its tables do not change a bit); the layout
+    schedule passes numpy's."""
+    timesteps = int(ac.shape[0])
+    c = timesteps // steps
+    ts = np.asarray(list(range(0, timesteps, c))) + 1
+    if ts.max() >= timesteps:
+        # same failure the reference hits (IndexError in make_ddim_sampling_parameters, SURVEY section 0)
+        raise IndexError('ddim_steps=%d yields timestep %d >= %d' % (steps, ts.max(), timesteps))
+    a = ac[ts]
+    prev_list = [ac[0].item()] + ac[ts[:-1]].tolist()
+    a_prev = torch.tensor(prev_list, dtype=torch.float32)
+    s1m = sqrt_1m(1.0 - a)
+    ap64 = np.asarray(prev_list, dtype=np.float64)
+    # (the reference evaluates ``ndarray / Tensor``, i.e. Tensor.__rtruediv__ = reciprocal(1 - alphas) in fp32, times the array)
+    sig64 = float(eta) * np.sqrt((1.0 - a).reciprocal().double().numpy() * (1 - ap64) * (1 - a.double().numpy() / ap64))
+    sig = torch.from_numpy(sig64).to(torch.float32)
+    cols = [s1m, a.sqrt(), a_prev.sqrt(), (1.0 - a_prev - sig ** 2).sqrt(), sig]
+    return dict(ts=ts, a=a, a_prev=a_prev, sqrt_one_minus_a=s1m, sigmas=sig, cols=cols)
 
 
 class ShapeSchedule:
     """DDIM coefficients, iteration i <-> index = S-1-i, timestep ts[index].  ``eta`` = 0 (the shipped call, echo2shape.py:484-521):
-    four coefficients per step; ``eta`` != 0: sigma_t as make_ddim_sampling_parameters derives it (ldm_diffusion_util.py:85-96: float64
-    arithmetic on the fp32 alphas, ``1 - alphas`` and its reciprocal formed in fp32 first, the result cast to fp32 when it is used) and
+    four coefficients per step; ``eta`` != 0: sigma_t as make_ddim_sampling_parameters derives it (ddim_tables) and
     sqrt(1 - a_prev - sigma_t^2) in fp32 as p_sample_ddim forms it (samplers/ddim.py:256): five coefficients per step."""
 
     def __init__(self, ddim_steps=100, timesteps=1000, linear_start=0.00085, linear_end=0.012, eta=0.0):
         betas = (torch.linspace(linear_start ** 0.5, linear_end ** 0.5, timesteps,
                                 dtype=torch.float64) ** 2).numpy()
         ac = torch.tensor(np.cumprod(1.0 - betas, axis=0), dtype=torch.float32)
-        c = timesteps // ddim_steps
-        ts = np.asarray(list(range(0, timesteps, c))) + 1
-        if ts.max() >= timesteps:
-            # same failure the reference hits (IndexError in make_ddim_sampling_parameters, SURVEY section 0)
-            raise IndexError('ddim_steps=%d yields timestep %d >= %d' % (ddim_steps, ts.max(), timesteps))
-        a = ac[ts]
-        prev_list = [ac[0].item()] + ac[ts[:-1]].tolist()
-        a_prev = torch.tensor(prev_list, dtype=torch.float32)
-        s1m = torch.sqrt(1.0 - a)
+        d = ddim_tables(ac, ddim_steps, eta)
+        ts = d['ts']
         self.eta = float(eta)
-        ap64 = np.asarray(prev_list, dtype=np.float64)
-        # (the reference evaluates ``ndarray / Tensor``, i.e. Tensor.__rtruediv__ = reciprocal(1 - alphas) in fp32, times the array)
-        sig64 = self.eta * np.sqrt((1.0 - a).reciprocal().double().numpy() * (1 - ap64) * (1 - a.double().numpy() / ap64))
-        sig = torch.from_numpy(sig64).to(torch.float32)
-        self.ddim_sigmas = sig
-        cols = [s1m, a.sqrt(), a_prev.sqrt(), (1.0 - a_prev - sig ** 2).sqrt()]
-        if self.eta != 0.0:
-            cols.append(sig)
-        tab = torch.stack(cols, dim=1)
+        self.ddim_sigmas = d['sigmas']
+        tab = torch.stack(d['cols'] if self.eta != 0.0 else d['cols'][:4], dim=1)
         order = np.arange(len(ts) - 1, -1, -1)
         self.ddim_timesteps = ts
         self.timesteps = ts[order]
@@ -140,6 +157,43 @@ class ShapeSchedule:
         self.sqrt_one_minus_alphas_cumprod = torch.tensor(np.sqrt(1.0 - ac64), dtype=torch.float32)
         tsi = torch.from_numpy(self.timesteps.copy())
         self.keep_tab = torch.stack([self.sqrt_alphas_cumprod[tsi], self.sqrt_one_minus_alphas_cumprod[tsi]], dim=1).contiguous()   # [S, 2] by iteration
+
+
+LAYOUT_SAMPLERS = ('ddpm', 'ddim')
+
+
+class LayoutDdimSchedule:
+    """Strided DDIM on the trained layout model: the reference's model-agnostic ``DDIMSampler`` (samplers/ddim.py) driven on the layout
+    denoiser, over ``layout_schedule``'s fp32 ``alphas_cumprod``.  Iteration i <-> index = S-1-i, timestep ts[index]; ``coef`` [S, 5] by
+    iteration = [sqrt(1-a), sqrt(a), sqrt(a_prev), sqrt(1-a_prev-sigma^2), sigma] (ddim_tables; sigma = 0 at ``eta`` = 0, where the update
+    reads no noise).  ``keep_tab`` [S, 2]: q_sample's two factors at those timesteps from the LAYOUT model's tables
+    (LayoutSchedule.sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod) -- DDIMSampler.ddim_sampling calls the model's own q_sample.
+    The iteration count is len(timesteps), not necessarily ``steps``.  ``model_var_type`` plays no part in DDIM and is ignored;
+    ``model_mean_type='x0'`` and ``clip_denoised=True`` have no reference arithmetic under DDIM and are refused."""
+
+    def __init__(self, layout_schedule, steps, eta=0.0, clip_denoised=False):
+        if layout_schedule.model_mean_type != 'eps':
+            raise ValueError("layout DDIM: model_mean_type=%r has no reference arithmetic under DDIM (p_sample_ddim takes the network "
+                             "output as eps)" % (layout_schedule.model_mean_type,))
+        if clip_denoised:
+            raise ValueError('layout DDIM: clip_denoised=True has no reference arithmetic under DDIM (p_sample_ddim never clips)')
+        steps = int(steps)
+        if steps < 1:
+            raise ValueError('layout_steps must be a positive integer, got %r' % (steps,))
+        self.base = layout_schedule
+        self.time_num = layout_schedule.time_num
+        self.eta = float(eta)
+        d = ddim_tables(layout_schedule.alphas_cumprod, steps, eta, sqrt_1m=lambda v: torch.from_numpy(np.sqrt(v.numpy())))
+        ts = d['ts']
+        order = np.arange(len(ts) - 1, -1, -1)
+        self.ddim_timesteps = ts
+        self.ddim_alphas, self.ddim_alphas_prev = d['a'], d['a_prev']
+        self.ddim_sqrt_one_minus_alphas, self.ddim_sigmas = d['sqrt_one_minus_a'], d['sigmas']
+        self.timesteps = ts[order]
+        self.coef = torch.stack(d['cols'], dim=1)[torch.from_numpy(order.copy())].contiguous()     # [S, 5] by iteration
+        tsi = torch.from_numpy(self.timesteps.copy())
+        self.keep_tab = torch.stack([layout_schedule.sqrt_alphas_cumprod[tsi], layout_schedule.sqrt_one_minus_alphas_cumprod[tsi]],
+                                    dim=1).contiguous()                                            # [S, 2] by iteration
 
 
 SHAPE_SAMPLERS = ('ddim', 'plms')

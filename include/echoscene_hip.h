@@ -298,6 +298,19 @@ typedef struct es_ddpm_keep_args {
     int32_t row;            /* floats per object (n % row == 0)                                 */
 } es_ddpm_keep_args;
 int es_ddpm_update_keep(const es_ddpm_keep_args* args, es_stream stream);
+/* Strided DDIM sampling of the layout branch: DDIMSampler.p_sample_ddim (samplers/ddim.py:236-262) on the rows [n / row, row] of the
+ * layout state, as ONE launch (es_ddim_update is two when it advances the step counter, and has no masked form).  The argument struct
+ * is es_ddpm_keep_args with coef = the five numbers of es_ddim_update per iteration, {sqrt(1-a_t), sqrt(a_t), sqrt(a_prev),
+ * sqrt(1-a_prev-sigma_t^2), sigma_t} (coef_stride >= 4; >= 5 with noise), and n_tab = the iterations of the strided schedule:
+ *   rows with mask 0, or every row when mask is NULL -- es_ddim_update's expressions in its order, the same bits:
+ *       pred_x0 = (x - c[0]*e)/c[1];  x <- c[2]*pred_x0 + c[3]*e  (+ c[4]*noise[step] when `noise` is given: eta != 0)
+ *     with e = the fixed-order slab sum of eps; no fp contraction;
+ *   rows with mask 1 -- exactly es_ddpm_update_keep's: the next iteration's tab[2 (step+1)] * x0 + tab[2 (step+1) + 1] *
+ *     keep_noise[step+1] while step + 1 < n_tab, x0 itself after the last iteration; they read neither eps nor noise.
+ * mask / x0 / keep_noise / tab are given together or are all NULL (the unmasked loop); noise may be NULL (eta = 0); clip_x0 != 0 is
+ * refused (p_sample_ddim never clips).  n <= 4096: one workgroup, which also advances the step counter; beyond: one workgroup per 256
+ * elements and the separate step increment.  The kept rows of x_T are primed with es_ddim_blend, as for es_ddpm_update_keep. */
+int es_ddim_rows_update(const es_ddpm_keep_args* args, es_stream stream);
 /* The inverse of es_box_postprocess: metric boxes -> the normalised rows of the layout state, so that a box of a dataset scene or of a
  * de-normalised result can be kept.  scale_box_params (helpers/util.py:516-532; ncol = 6: sizes | translations, ncol = 7: also column
  * 6, a metric angle, its ``angle`` flag :528-530): out[o, c] = 2 (boxes[o, c] - lo_c) / (hi_c - lo_c) - 1, and preprocess_angle2sincos
@@ -539,8 +552,10 @@ enum {
     ES_OP_CONV_C1 = 19,                           /* es_conv_c1_f32 (es_conv_c1_args): the VQ-VAE encoder's one-channel conv_in */
     ES_OP_DDPM_KEEP = 21,                         /* es_ddpm_update_keep (es_ddpm_keep_args): the layout update that also carries the kept rows.
                                                      (20 stays unassigned: es_op_pointer_offsets(20) is pinned to "unknown kind") */
-    ES_OP_PLMS = 23, ES_OP_PLMS_FIRST_A = 24, ES_OP_PLMS_FIRST_B = 25    /* es_plms_update / es_plms_first_a / es_plms_first_b (es_plms_args);
+    ES_OP_PLMS = 23, ES_OP_PLMS_FIRST_A = 24, ES_OP_PLMS_FIRST_B = 25,   /* es_plms_update / es_plms_first_a / es_plms_first_b (es_plms_args);
                                                      22 stays unassigned, as 20: es_op_pointer_offsets(22) is pinned to "unknown kind" */
+    ES_OP_DDIM_ROWS = 27                          /* es_ddim_rows_update (es_ddpm_keep_args): the strided DDIM update of the layout loop, masked
+                                                     or not.  26 stays unassigned, as 20 and 22 (pinned to "unknown kind") */
 };
 /* Row select: out[r, 0..n) = table[*step, 0..n) for r < rows.  The timestep-dependent but node-independent products of a
  * denoiser (time MLP, all ResBlock emb projections, box/shape time embedding) are tabulated once per schedule
@@ -631,6 +646,8 @@ int es_sampler_run(es_plan* plan, int32_t* step, int first_step, int n_steps, in
  *   shape model :  "x" [O,3,16,16,16] latents, "step" int32
  *   layout model saved with keep=True (the masked loop, es_layout_sample_keep): also "x0" [O,8], "mask" [O], "knoise" [T,O,8]
  *                  (q_sample's draws, row i = iteration i) and "ktab" [T,2] (es_ddpm_keep_args.tab)
+ *   layout model of a strided DDIM loop (LayoutDenoiser(sampler='ddim'); es_ddim_rows_update is its last op): the same regions with T =
+ *                  the iterations of the strided schedule; "noise" rows 1+i are read only when eta != 0
  *   both loops  :  "coef" = the schedule's coefficient table [n_steps][coef_stride]: es_model_run / es_layout_sample / es_shape_sample
  *                  refuse to run past its last row
  *   vq model    :  "z" [O,3,16,16,16] input latents, "sdf" [O,1,64,64,64] output

@@ -1,8 +1,9 @@
 #!/usr/bin/env python
 """Scene calls over a sequence of scene sizes through the drop-in API (the reference's eval loop walks scenes of different
 object counts): first call at a new size (plan build + graph capture) against the repeated call.
-usage: python tools/scene_sizes_latency.py [sizes, default 32,10,16,10,6,16] [--shape-sampler ddim|plms] [--shape-steps K] [--repeats N] [--alternate]
-(--shape-sampler / --shape-steps: the keywords of the same names of sample_box_and_shape; --repeats: calls per size, default 2)"""
+usage: python tools/scene_sizes_latency.py [sizes, default 32,10,16,10,6,16] [--shape-sampler ddim|plms] [--shape-steps K] [--layout-sampler ddpm|ddim] [--layout-steps K] [--repeats N] [--alternate]
+(--shape-sampler / --shape-steps / --layout-sampler / --layout-steps: the keywords of the same names of sample_box_and_shape;
+--repeats: calls per size, default 2)"""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -14,11 +15,14 @@ ap = argparse.ArgumentParser()
 ap.add_argument('sizes', nargs='?', default='32,10,16,10,6,16')
 ap.add_argument('--shape-sampler', default=None)
 ap.add_argument('--shape-steps', type=int, default=None)
+ap.add_argument('--layout-sampler', default=None)
+ap.add_argument('--layout-steps', type=int, default=None)
 ap.add_argument('--repeats', type=int, default=2)
 ap.add_argument('--alternate', action='store_true', help='after each size also make the default call: both denoisers resident')
 cli = ap.parse_args()
 sizes = [int(x) for x in cli.sizes.split(',')]
-skw = {k: v for k, v in (('shape_sampler', cli.shape_sampler), ('shape_steps', cli.shape_steps)) if v is not None}
+skw = {k: v for k, v in (('shape_sampler', cli.shape_sampler), ('shape_steps', cli.shape_steps), ('layout_sampler', cli.layout_sampler),
+                          ('layout_steps', cli.layout_steps)) if v is not None}
 opt = escfg.default_diff_opt('cuda', concat=False)
 m = SGDiff('echoscene', opt, synth.VOCAB, replace_latent=False, with_changes=True, residual=True, gconv_pooling='avg',
            with_angles=True, clip=True, separated=False)
