@@ -533,6 +533,7 @@ __device__ __forceinline__ void conv_epilogue(const es_conv_args& a, const ConvG
     const bool geglu_epi = EPI_ < 0 ? a.epilogue == ES_EPI_GEGLU : EPI_ == ES_EPI_GEGLU;
     if constexpr (!ACTIVE) {
         __syncthreads();
+        if constexpr (STATS_ && WROWS == 32) __syncthreads();     // (the half tile's consumers exchange their half-group sums, below)
         return;
     }
     const int wm = wave >> 1, wn = wave & 1, i16 = lane & 15, q = lane >> 4;
@@ -740,15 +741,32 @@ __device__ __forceinline__ void conv_epilogue(const es_conv_args& a, const ConvG
             if constexpr (STATS_) {
                 // One (sum, sum of squares) pair per column for the wave's 64 rows: the even rows were summed top to bottom by lanes
                 // 0..27, the odd rows by lanes 28..55; even + odd is the order k_rowgroup_stats repeats.
-                static_assert(WROWS == 64, "row groups of gn_stats_out are 64 rows");
+                static_assert(WROWS == 64 || (WROWS == 32 && FOLD_), "row groups of gn_stats_out are 64 rows");
                 f4 os, oq;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { os[e] = __shfl(gs[e], lane + 28); oq[e] = __shfl(gq[e], lane + 28); }
+                if constexpr (WROWS == 64) {
                 if (lane < 28 && n_ok && rows_left > 0) {
                     const unsigned nrg = (unsigned)((M + 63) >> 6);
                     const unsigned so = (unsigned)(mw0 >> 6) * (unsigned)a.N + (unsigned)n;
                     *(f4*)&a.gn_stats_out[so] = gs + os;
                     *(f4*)&a.gn_stats_out[so + nrg * (unsigned)a.N] = gq + oq;
+                }
+                } else {
+                    // The half tile of k_conv_ws_fold's balanced schedule: 32-row waves, so a 64-row group is the rows of the waves
+                    // (wm, wn) and (wm + 1, wn), wm even.  The lower half's sums go through LDS behind the slabs (all 12 waves
+                    // meet at the barrier: the producers wait in their branch above); the upper wave adds its own on top -- rows
+                    // 0..31 before rows 32..63.  The host sends only launches with M % 128 == 0 here: every wave holds 32 valid rows.
+                    f4* const xch = (f4*)(smem + NW_ * (16 * 116) * 4) + (wave * 28 + (lane < 28 ? lane : 0)) * 2;
+                    if (!(wm & 1) && lane < 28) { xch[0] = gs + os; xch[1] = gq + oq; }
+                    __syncthreads();
+                    if ((wm & 1) && lane < 28 && n_ok && rows_left > 0) {
+                        const f4* const lo = xch - 2 * 28 * 2;                // wave - 2: (wm - 1, wn)
+                        const unsigned nrg = (unsigned)((M + 63) >> 6);
+                        const unsigned so = (unsigned)(mw0 >> 6) * (unsigned)a.N + (unsigned)n;
+                        *(f4*)&a.gn_stats_out[so] = lo[0] + (gs + os);
+                        *(f4*)&a.gn_stats_out[so + nrg * (unsigned)a.N] = lo[1] + (gq + oq);
+                    }
                 }
             }
         }
@@ -1487,6 +1505,26 @@ __global__ __launch_bounds__(768, 3) void k_conv_ws_fold(const es_conv_args a, c
     int bx, by, bz;
     conv_tile_of(a, bx, by, bz);
     conv_ws_tile<256, 8, 4, true, ES_EPI_NONE, STATS_, 3, true>(a, g, 0, smem, wave, lane, M, bx, by, 0, 12 * (a.Cin >> 5), 1, 0, stamp);
+}
+
+// The balanced schedule of k_conv_ws_fold for launches with THREE column tiles whose grid of 256-row tiles leaves its last round
+// of workgroups mostly empty (ConvRoute::fold_bal: 384 tiles on 256 CUs are two rounds, the second half idle).  Grid (row tiles, 2):
+// workgroup (r, p) computes the 256 x 224 tile (r, column tile p) and then rows [128 p, 128 p + 128) of tile (r, column tile 2) as a
+// 128-row tile with the same 12 waves (consumers 4 x 2 of 32 x 112) -- one round of 1.5 tiles per workgroup.  Every output element
+// is still formed by ONE workgroup over the whole folded K range in the same unit order: no slabs, no reduction, the same bits.
+// D Hi Wi % 256 == 0 (the folded route's condition) keeps a half tile inside one parity class of one object.
+template <bool STATS_>
+__global__ __launch_bounds__(768, 3) void k_conv_ws_fold_bal(const es_conv_args a, const ConvGeom g) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const long M = (long)g.O * g.D * g.H * g.W;
+    int bx, by, bz;
+    conv_tile_of(a, bx, by, bz);
+    const int nks = 12 * (a.Cin >> 5);
+    conv_ws_tile<256, 8, 4, true, ES_EPI_NONE, STATS_, 3, true>(a, g, 0, smem, wave, lane, M, bx, by, 0, nks, 1, 0, nullptr);
+    __syncthreads();                             // the consumers' epilogue slabs lie in the ring the producers fill next
+    conv_ws_tile<128, 8, 4, true, ES_EPI_NONE, STATS_, 3, true>(a, g, 0, smem, wave, lane, M, 2 * bx + by, 2, 0, nks, 1, 0, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3007,6 +3045,7 @@ struct ConvRoute {
     bool stats_pass;           // k_rowgroup_stats over the finished output forms gn_stats_out
     int slabs;                 // es_conv_split_of: fp32 slabs [slabs][M][N] written into the workspace (a chunked launch: in units of the
                                // whole M x N; 0: a direct kernel, no workspace; for linear_deep the automatic split it stands in for)
+    bool fold_bal;             // ws_256_up_fold on its balanced schedule (k_conv_ws_fold_bal, grid (row tiles, 2); es_conv_fold_balanced)
 };
 }  // namespace
 
@@ -3297,8 +3336,17 @@ static int conv_route(const es_conv_args* a, ConvRoute* r) {
             // canonical and the sharded arithmetic stay the 27-tap one) whose 256-row tiles are each one parity class of one object.
             // Other products than the 27-tap route's (the folded weights are rounded after the sum): not bit-equal to it.
             if (r->kernel == ConvKernel::ws_256_8_4_3 && a->mode == ES_CONV_UP_HW && a->w2 && !a->a2 && S == 1 && a->O_hint == 0 &&
-                a->H >= 2 && a->W >= 2 && ((long)a->D * g.Hi * g.Wi) % 256 == 0)
+                a->H >= 2 && a->W >= 2 && ((long)a->D * g.Hi * g.Wi) % 256 == 0) {
                 r->kernel = ConvKernel::ws_256_up_fold;
+                // three column tiles, no workspace, on a grid whose last round of 256 workgroups is mostly empty (384 tiles: 75 % of two rounds):
+                // 2 workgroups per row tile, each one whole tile and half of the third column tile (k_conv_ws_fold_bal) -- the same
+                // sums in the same order, S stays 1
+                const long rounds = (wg256 + 255) / 256;
+                if (ntn == 3 && !a->workspace && M % 256 == 0 && (double)wg256 / (double)(rounds * 256) < 0.8) {
+                    r->fold_bal = true;
+                    r->grid = dim3(r->grid.x, 2, 1);
+                }
+            }
         } else
             r->kernel = ConvKernel::lean_256;
     } else if ((wg128 >= 512 || S > 1) && !tiny_split) {
@@ -3385,7 +3433,8 @@ static int conv_launch(const es_conv_args* a, const ConvRoute& r, hipStream_t st
                                {(const void*)k_linear_deep, LDSDEEP},
                                {(const void*)k_linear_ws<ES_EPI_NONE>, LDSLIN}, {(const void*)k_linear_ws<ES_EPI_GEGLU>, LDSLIN},
                                {(const void*)k_conv_ws3<false>, LDSWS3}, {(const void*)k_conv_ws3<true>, LDSWS3},
-                               {(const void*)k_conv_ws_fold<false>, LDS256}, {(const void*)k_conv_ws_fold<true>, LDS256}};
+                               {(const void*)k_conv_ws_fold<false>, LDS256}, {(const void*)k_conv_ws_fold<true>, LDS256},
+                               {(const void*)k_conv_ws_fold_bal<false>, LDS256}, {(const void*)k_conv_ws_fold_bal<true>, LDS256}};
     ES_REQUIRE(lim.err == hipSuccess, "es_conv_mfma_f16: hipFuncSetAttribute failed: %s", hipGetErrorString(lim.err));
     // (the queries answer for such a route; only the launch refuses it)
     ES_REQUIRE(r.kernel != ConvKernel::none, "es_conv_mfma_f16: %s", r.omax ? "a chunked route is launched chunk by chunk" : r.unbuilt);
@@ -3413,7 +3462,10 @@ static int conv_launch(const es_conv_args* a, const ConvRoute& r, hipStream_t st
         else hipLaunchKernelGGL((k_conv_ws3<false>), r.grid, dim3(768), LDSWS3, st, *a, r.g);
         break;
     case ConvKernel::ws_256_up_fold:
-        if (r.stats) hipLaunchKernelGGL((k_conv_ws_fold<true>), r.grid, dim3(768), LDS256, st, *a, r.g);
+        if (r.fold_bal) {
+            if (r.stats) hipLaunchKernelGGL((k_conv_ws_fold_bal<true>), r.grid, dim3(768), LDS256, st, *a, r.g);
+            else hipLaunchKernelGGL((k_conv_ws_fold_bal<false>), r.grid, dim3(768), LDS256, st, *a, r.g);
+        } else if (r.stats) hipLaunchKernelGGL((k_conv_ws_fold<true>), r.grid, dim3(768), LDS256, st, *a, r.g);
         else hipLaunchKernelGGL((k_conv_ws_fold<false>), r.grid, dim3(768), LDS256, st, *a, r.g);
         break;
     case ConvKernel::linear_ws:
@@ -3510,6 +3562,14 @@ extern "C" int es_conv_kernel_of(const es_conv_args* a, char* name_out, int cap)
     if (conv_route(a, &r) != 0) return -1;
     if (name_out && cap > 0) snprintf(name_out, (size_t)cap, "%s", r.omax ? "chunked" : kConvKernelName[(int)r.kernel]);
     return r.S > 1 ? r.S : 1;
+}
+
+// 1 when es_conv_mfma_f16(args) takes the folded route on its balanced schedule (ConvRoute::fold_bal: three column tiles on a grid
+// whose last round is mostly empty -- two workgroups per row tile, each one tile and a half), 0 when not, -1 on invalid arguments.
+// Host-only; the kernel name and the split that es_conv_kernel_of reports do not depend on it.
+extern "C" int es_conv_fold_balanced(const es_conv_args* a) {
+    ConvRoute r;
+    return conv_route(a, &r) == 0 ? (int)r.fold_bal : -1;
 }
 
 extern "C" int es_groupnorm_vol(const es_gn_args* a, es_stream stream) {

@@ -253,9 +253,12 @@ class VolBuilderMixin:
         return len(self.ops) - 1
 
     def conv(self, a_f16, pc, O, dims, mode=hip.CONV_SAME, bias=None, rowvec=None, res=None, out_f32=None,
-             out_f16=None, skip=None, ncdhw=False, splitk=None, epilogue=0, out_ld=None):
-        """dims = (D,H,W) of the OUTPUT grid. skip = (raw_f16 tensor, PackedConv) for the fused 1x1 skip."""
+             out_f16=None, skip=None, ncdhw=False, splitk=None, epilogue=0, out_ld=None, w_fold=None):
+        """dims = (D,H,W) of the OUTPUT grid. skip = (raw_f16 tensor, PackedConv) for the fused 1x1 skip.  ``w_fold``: the folded
+        image of an ES_CONV_UP_HW conv (PackedConv.w_fold; es_conv_args.w2) -- known here, BEFORE the split-K workspace is offered:
+        a launch that the library sends to the folded kernel when it is unsplit stays without a workspace."""
         D, H, W = dims
+        assert w_fold is None or (skip is None and mode == hip.CONV_UP_HW)
         if getattr(self, 'fp32x', False) and a_f16.dtype == torch.float32:
             # split-operand route: the fp32 operand(s) -> [hi | lo | hi] f16 images, then the ordinary f16 launch on 3 Cin channels; an
             # f16 operand copy of the output is the fp32 output itself, as on the fp32 route
@@ -292,7 +295,18 @@ class VolBuilderMixin:
         # eligibility from the WHOLE (or reference) problem's row count (O_hint): a shard and the unsharded run must take the same
         # can_split decision, or the library picks S from the global tile count for one and S = 1 for the other
         Mh = (-a.O_hint if a.O_hint < 0 else max(a.O_hint, O)) * D * H * W
-        if not ncdhw and Mh * pc.N <= 8192 * 5376 and pc.N % 4 == 0 and not epilogue:
+        folded = False
+        if w_fold is not None:
+            # the folded route takes unsplit launches only: ask the library what THIS launch does without a workspace (a, as filled so
+            # far: workspace NULL, splitk 0).  Where it names the folded kernel the op stays that way -- 12 taps unsplit beat 27 taps
+            # split (profiles/up_fold_notes.md); everywhere else the launch gets workspace and split as any other conv
+            a.w2 = w_fold.data_ptr()
+            self.keep.append(w_fold)
+            name = C.create_string_buffer(32)
+            if hip.lib().es_conv_kernel_of(C.byref(a), name, 32) < 0:
+                raise RuntimeError('es_conv_kernel_of: ' + hip.lib().es_last_error().decode())
+            folded = name.value == b'ws_256_up_fold'
+        if not folded and not ncdhw and Mh * pc.N <= 8192 * 5376 and pc.N % 4 == 0 and not epilogue:
             a.splitk = -1 if splitk is None else splitk
             a.workspace = 1                                  # (any non-NULL value: es_conv_split_of only asks whether there is one)
             S = hip.lib().es_conv_split_of(C.byref(a))       # round 6: the library says how many slabs it will write
@@ -833,15 +847,15 @@ def emit_unet3d_step(b, w, g, x, uc_dev, temb, step, eps_out, dims=(16, 16, 16),
                 a16 = need_f16()
                 nd = (dm[0] * 2, dm[1] * 2, dm[2] * 2) if w.concat else (dm[0], dm[1] * 2, dm[2] * 2)
                 o = sbuf(O * V_(nd), state['C'])
-                state['last_op'] = b.conv(a16, d['conv'], O, nd, mode=hip.CONV_UP_DHW if w.concat else hip.CONV_UP_HW, out_f32=o)
                 wf = getattr(d['conv'], 'w_fold', None)
-                if (wf is not None and getattr(b, 'up_fold', False) and not w.concat and not b.fp32
+                if not (wf is not None and getattr(b, 'up_fold', False) and not w.concat and not b.fp32
                         and not int(getattr(b, 'o_hint', 0) or 0)):
-                    # the folded image rides in w2 (no up-sampling conv has a skip phase); the op, its taps and its plan signature stay
-                    # as they are and the library takes the folded route where the launch is eligible (conv_route: ws_256_up_fold).
-                    # Not under o_hint: the canonical / sharded arithmetic is the 27-tap one
-                    b.ops[state['last_op']].u.conv.w2 = wf.data_ptr()
-                    b.keep.append(wf)
+                    wf = None
+                # the folded image rides in w2 (no up-sampling conv has a skip phase); the op, its taps and its plan signature stay
+                # as they are and the library takes the folded route where the launch is eligible (conv_route: ws_256_up_fold) --
+                # Builder.conv() withholds the split-K workspace from exactly those launches.
+                # Not under o_hint: the canonical / sharded arithmetic is the 27-tap one
+                state['last_op'] = b.conv(a16, d['conv'], O, nd, mode=hip.CONV_UP_DHW if w.concat else hip.CONV_UP_HW, out_f32=o, w_fold=wf)
                 state.update(h=o, dims=nd, h16=None)
             b.tags[name] = View(state['h'])
 

@@ -352,7 +352,11 @@ typedef struct es_conv_args {
        multiplies through the folded image on one route only (an unsplit launch on the 256-row producer/consumer tiles with
        O_hint == 0 and D * H/2 * W/2 % 256 == 0; es_conv_kernel_of: "ws_256_up_fold") and ignores it on every other, the fp32
        entry point included.  The folded weights are rounded to f16 after the sum, so that route is not bit-equal to the 27-tap
-       one: a caller that needs the canonical arithmetic leaves w2 NULL (ShapeDenoiser(up_fold=False), deterministic=True) */
+       one: a caller that needs the canonical arithmetic leaves w2 NULL (ShapeDenoiser(up_fold=False), deterministic=True).
+       "Unsplit" is the caller's to arrange: a launch that is handed a `workspace` may be split by the tile-quantisation rule and
+       then keeps its 27-tap route.  A planner asks es_conv_kernel_of with w2 set and workspace NULL first and offers the
+       workspace only where the answer is not "ws_256_up_fold" (Builder.conv(w_fold=...)).  Without a workspace, a launch with three
+       column tiles whose grid fills under 80 % of its rounds of 256 workgroups runs the balanced schedule (es_conv_fold_balanced) */
     const float* bias;        /* [N] (sum of both biases when a2 is used) or NULL                */
     const float* rowvec;      /* [O, rowvec_ld] per-object vector broadcast over voxels (emb_layers output /
                                  cross-attention-with-one-key output), or NULL                   */
@@ -416,6 +420,11 @@ int es_conv_split_of(const es_conv_args* args);
  * built) into name_out (cap bytes, always terminated) and returns the split of K over workgroups (>= 1; a chunked launch: of a full
  * chunk); -1 on invalid arguments.  For tests and tools: the answer is no part of the numerics contract.  Launches nothing. */
 int es_conv_kernel_of(const es_conv_args* args, char* name_out, int cap);
+/* 1 when es_conv_mfma_f16(args) takes the folded route ("ws_256_up_fold") on its balanced schedule: a launch with three column tiles
+ * and no workspace whose grid of 256-row tiles fills under 80 % of its rounds of 256 workgroups runs two workgroups per row tile, each one whole tile
+ * and half of the third column tile.  The same sums in the same order as the plain schedule; the name and the split reported by
+ * es_conv_kernel_of do not change.  0 when not, -1 on invalid arguments.  For tests and tools.  Launches nothing. */
+int es_conv_fold_balanced(const es_conv_args* args);
 /* Split-operand image of an fp32 activation [M, C] (C % 4 == 0): out f16 [M, 3 C] = [hi | lo | hi], hi = f16(x), lo = f16(x - hi).
  * Against a weight image packed from [w_hi | w_hi | w_lo] (Cin = 3 C) es_conv_mfma_f16 accumulates hi w_hi + lo w_hi + hi w_lo in
  * fp32: the reference's fp32 arithmetic to ~2^-21 per product on the f16 matrix pipe (ShapeDenoiser(precision='fp32x')). */

@@ -2,6 +2,8 @@
 would make (fused groups) and checks, from the pointers alone, that
   * the problems of one launch are independent (none reads or overwrites what another writes), and
   * every operand a launch reads was produced by an EARLIER launch (or is an input of the step).
+emit_shape_step_cpu() emits the shape loop step (full-width UNet3D) the same way, for checks of what the planner asks of the library
+(tests/test_up_fold_second_cpu.py).
 Usage: python tools/plan_dryrun.py [model_channels] [nodes]"""
 import os
 import sys
@@ -29,6 +31,38 @@ def emit_layout_step_cpu(mc=128, O=8, enable_t_emb=True, concat=False, seed=3):
     tables = dict(emb=None, emb_all=torch.zeros(n_steps, w.emb_all.N), t_lin=torch.zeros(n_steps, 64) if enable_t_emb else None)
     bufs = emit_layout_step(b, w, g, torch.randn(O, 640), torch.zeros(n_steps, mc), tables, n_steps, eps_out=eps)
     return b, dict(x=bufs['x'], eps=eps, step=bufs['step'])
+
+
+def emit_shape_step_cpu(O=32, width=224, precision='fp16', up_fold=True, deterministic=False, seed=100, weights=None):
+    """the shape loop step (samplers.emit_shape_step, as ShapeDenoiser._build_state emits it for one GPU) of the UNet3D of
+    ``width`` model channels on a CPU Builder.  ``weights``: packed UNet3DWeights of an earlier call with the same precision
+    (packing the full-width network on the host takes seconds).  Returns (Builder, weights)."""
+    from echoscene_amd import synth, config as escfg
+    from echoscene_amd.model.unet import DiffusionUNet
+    from echoscene_amd.plan import Builder, GraphIndex
+    from echoscene_amd.plan_vol import UNet3DWeights
+    from echoscene_amd.samplers import _cap, _cpu_sd, emit_shape_step, CANON_OBJECTS
+    dev = torch.device('cpu')
+    w = weights
+    if w is None:
+        df = DiffusionUNet(escfg.shape_df_conf(width).unet.params, conditioning_key='crossattn')
+        synth.seeded_fill_(df, prefix='dry.shape.')
+        sd = {k[len('diffusion_net.'):]: v for k, v in _cpu_sd(df).items()}
+        w = UNet3DWeights(sd, df.diffusion_net, dev, precision)
+    assert w.precision == precision
+    _, triples = synth.synthetic_graph(O, seed=seed)
+    g = GraphIndex(triples, O, dev, capacity=_cap(triples.shape[0]))
+    b = Builder(dev)
+    b.shard_block, b.force_exchange = O, False
+    b.up_fold = up_fold and not deterministic
+    if deterministic:
+        b.o_hint = -CANON_OBJECTS
+    S = 4
+    tables = dict(emb=None, emb_all=torch.zeros(S, w.emb_all.N), t_lin=torch.zeros(S, 64))
+    uc = torch.zeros(O, 1280)
+    emit_shape_step(b, w, g, uc, torch.zeros(S, w.mc), tables, torch.zeros(S, 8), torch.zeros(S, 2), S, (3, 16, 16, 16), 0, O,
+                    gather_rows=O)
+    return b, w
 
 
 def _linear_io(a, hip):
