@@ -79,6 +79,7 @@ static int dispatch(const es_op& op, hipStream_t s) {
         case ES_OP_PLMS_FIRST_A: return es_plms_first_a(&op.u.plms, s);
         case ES_OP_PLMS_FIRST_B: return es_plms_first_b(&op.u.plms, s);
         case ES_OP_DDIM_ROWS: return es_ddim_rows_update(&op.u.keep, s);
+        case ES_OP_DDIM_BLEND_VOX: return es_ddim_blend_vox(&op.u.blend_vox, s);
         default: es_set_error("plan: unknown op kind %d", op.kind); return 3;
     }
 }
@@ -289,6 +290,10 @@ extern "C" int es_op_pointer_offsets(int kind, size_t* out, int cap) {
         case ES_OP_ROWSEL: v = {ES_PTR(rowsel.table), ES_PTR(rowsel.step), ES_PTR(rowsel.out)}; break;
         case ES_OP_DDIM_BLEND:
             v = {ES_PTR(blend.x), ES_PTR(blend.x0), ES_PTR(blend.mask), ES_PTR(blend.noise), ES_PTR(blend.tab), ES_PTR(blend.step)};
+            break;
+        case ES_OP_DDIM_BLEND_VOX:
+            v = {ES_PTR(blend_vox.x), ES_PTR(blend_vox.x0), ES_PTR(blend_vox.mask), ES_PTR(blend_vox.noise), ES_PTR(blend_vox.tab),
+                 ES_PTR(blend_vox.step)};
             break;
         case ES_OP_CONV_C1:
             v = {ES_PTR(conv_c1.x), ES_PTR(conv_c1.w), ES_PTR(conv_c1.bias), ES_PTR(conv_c1.out_f32), ES_PTR(conv_c1.out_f16)};

@@ -118,6 +118,14 @@ OP_PLMS, OP_PLMS_FIRST_A, OP_PLMS_FIRST_B = 23, 24, 25     # PLMS sampling of th
 OP_DDIM_ROWS = 27                          # the strided DDIM update of the layout loop, masked or not (csrc/es_layout_ddim.hip; DdpmKeepArgs); 26 stays unassigned
 
 
+OP_DDIM_BLEND_VOX = 28                     # masked-DDIM blend with a mask per latent voxel: shape completion (csrc/es_complete.hip)
+
+
+class BlendVoxArgs(C.Structure):
+    _fields_ = [('x', C.c_void_p), ('x0', C.c_void_p), ('mask', C.c_void_p), ('noise', C.c_void_p), ('noise_stride', C.c_int32),
+                ('tab', C.c_void_p), ('step', C.c_void_p), ('O', C.c_int32), ('C', C.c_int32), ('V', C.c_int32)]
+
+
 class PlmsArgs(C.Structure):
     _fields_ = [('x', C.c_void_p), ('eps', C.c_void_p), ('eps_nslab', C.c_int32), ('eps_slab_stride', C.c_int32),
                 ('coef', C.c_void_p), ('coef_stride', C.c_int32), ('n', C.c_int32), ('step', C.c_void_p),
@@ -142,7 +150,7 @@ class _OpU(C.Union):
     _fields_ = [('linear', LinearArgs), ('update', UpdateArgs), ('copy', CopyArgs), ('conv', ConvArgs),
                 ('gn', GNArgs), ('ln', LNArgs), ('attn', AttnArgs), ('geglu', GegluArgs), ('tocl', ToClArgs),
                 ('stem', StemArgs), ('vq', VQArgs), ('rowsel', RowSelArgs), ('blend', BlendArgs), ('conv_c1', ConvC1Args),
-                ('keep', DdpmKeepArgs), ('plms', PlmsArgs)]
+                ('keep', DdpmKeepArgs), ('plms', PlmsArgs), ('blend_vox', BlendVoxArgs)]
 
 
 class Op(C.Structure):
@@ -181,6 +189,9 @@ EXPORTS = {
     'es_ddpm_update': (C.c_int, [C.POINTER(UpdateArgs), C.c_void_p]),
     'es_ddim_update': (C.c_int, [C.POINTER(UpdateArgs), C.c_void_p]),
     'es_ddim_blend': (C.c_int, [C.POINTER(BlendArgs), C.c_void_p]),
+    'es_ddim_blend_vox': (C.c_int, [C.POINTER(BlendVoxArgs), C.c_void_p]),
+    'es_range_mask': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'es_partial_shape': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'es_conv_c1_f32': (C.c_int, [C.POINTER(ConvC1Args), C.c_void_p]),
     'es_ddpm_update_keep': (C.c_int, [C.POINTER(DdpmKeepArgs), C.c_void_p]),
     'es_ddim_rows_update': (C.c_int, [C.POINTER(DdpmKeepArgs), C.c_void_p]),

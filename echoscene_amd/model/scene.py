@@ -33,6 +33,7 @@ def _dev(module):
 
 _BOX_OPTS = ('keep_box_nodes', 'keep_boxes', 'keep_box_noise')
 _LAYOUT_OPTS = ('layout_sampler', 'layout_steps', 'layout_eta')
+_COMPLETE_OPTS = ('complete_nodes', 'complete_sdfs', 'complete_ranges', 'complete_masks')
 
 
 def _hip_device(d):
@@ -254,6 +255,65 @@ class EchoToShape(object):
         if rows:
             x0[rows] = self._encoder().encode_no_quant(sel, sync=False)
         return x0, mask.to(device), rows, sel
+
+    def check_complete(self, complete_nodes=None, complete_sdfs=None, complete_ranges=None, complete_masks=None, keep_nodes=None,
+                       gen_shape=True):
+        """The ``complete_*`` keywords of the sampling calls, validated on the host (no device work; every refusal is a ValueError):
+        returns None without them, else (nodes, sdfs, ranges or None, masks or None) with one entry per entry of ``complete_nodes``."""
+        given = [k for k, v in zip(_COMPLETE_OPTS, (complete_nodes, complete_sdfs, complete_ranges, complete_masks)) if v is not None]
+        if not given:
+            return None
+        if complete_nodes is None or complete_sdfs is None:
+            raise ValueError('complete_nodes and complete_sdfs go together (got %s)' % ', '.join(given))
+        if not gen_shape:
+            raise ValueError('complete_nodes / complete_sdfs complete SHAPES: they need gen_shape=True')
+        if (complete_ranges is None) == (complete_masks is None):
+            raise ValueError('shape completion needs exactly one of complete_ranges (xyz ranges) and complete_masks (latent masks); '
+                             'got %s' % ('both' if complete_ranges is not None else 'neither'))
+        as_list = lambda v: [int(t) for t in (v.tolist() if torch.is_tensor(v) else v)]
+        nodes = as_list(complete_nodes)
+        both = sorted(set(nodes) & set(as_list(keep_nodes) if keep_nodes is not None else ()))
+        if both:
+            raise ValueError('nodes %s are in keep_nodes and in complete_nodes: a shape is kept whole or completed, not both' % both)
+        sdfs = torch.as_tensor(complete_sdfs)
+        if sdfs.dim() != 5 or sdfs.shape[0] != len(nodes) or sdfs.shape[1] != 1:
+            raise ValueError('complete_sdfs must be [len(complete_nodes), 1, D, H, W] (one truncated SDF per entry of complete_nodes); '
+                             'got %s for %d nodes' % (tuple(sdfs.shape), len(nodes)))
+        zd = tuple(int(d) for d in self.z_shape[1:])
+        if complete_ranges is not None:
+            from ..postprocess import range_bounds
+            ranges = [complete_ranges] if isinstance(complete_ranges, dict) else list(complete_ranges)
+            if len(ranges) != len(nodes):
+                raise ValueError('complete_ranges must hold one xyz range per entry of complete_nodes; got %d for %d nodes'
+                                 % (len(ranges), len(nodes)))
+            range_bounds(ranges, zd[0])                              # (the form of every entry)
+            return nodes, sdfs, ranges, None
+        masks = torch.as_tensor(complete_masks)
+        if tuple(masks.shape) != (len(nodes), 1) + zd:
+            raise ValueError('complete_masks must be [len(complete_nodes), 1, %d, %d, %d] (latent space, one value for all channels); '
+                             'got %s for %d nodes' % (zd + (tuple(masks.shape), len(nodes))))
+        if not bool(((masks == 0) | (masks == 1)).all()):
+            raise ValueError('complete_masks: 0 (generate) or 1 (keep) per latent voxel')
+        return nodes, sdfs, None, masks
+
+    def complete_inputs(self, checked, x0, mask, device):
+        """The completed nodes into the inputs of the masked loop: ``checked`` from check_complete, ``x0`` [O, C, D, H, W] and the
+        per-object ``mask`` [O] of the kept nodes (keep_inputs; zeros without any).  Returns (x0, the voxel mask [O, 1, D, H, W]): a kept
+        node is an all-ones row, a completed node carries the encoding of its WHOLE SDF (shape_comp, sdfusion_model.py:411-418) and
+        the latent mask of its range.  Duplicates and out-of-range entries as samplers.keep_selection."""
+        from ..samplers import keep_selection
+        from ..postprocess import latent_range_mask
+        nodes, sdfs, ranges, masks = checked
+        O, zd = x0.shape[0], tuple(int(d) for d in self.z_shape[1:])
+        vm = mask.to(device).float().reshape(O, 1, 1, 1, 1).expand(O, 1, *zd).contiguous()
+        _, rows, src = keep_selection(nodes, O)
+        if rows:
+            x0[rows] = self._encoder().encode_no_quant(sdfs[src].to(device).float().contiguous(), sync=False)
+            if ranges is not None:
+                vm[rows] = latent_range_mask([ranges[k] for k in src], zd, device)
+            else:
+                vm[rows] = masks[src].to(device).float()
+        return x0, vm
 
     def _decoder(self):
         if self._dec is None:
@@ -523,7 +583,7 @@ class Sg2ScDiffModel(_SceneModel):
     def _layout_and_shapes(self, gen_shape, dec_objs, dec_triples, obj_embed_, latent, layout_noise, shape_noise, *,
                            keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None, keep_boxes=None,
                            keep_box_noise=None, shape_sampler=None, shape_steps=None, layout_sampler=None, layout_steps=None,
-                           layout_eta=None):
+                           layout_eta=None, complete_nodes=None, complete_sdfs=None, complete_ranges=None, complete_masks=None):
         """The two loops only share the setup (the reference runs them back to back, EchoScene.py:402-419).  Here they are
         ONE replayed hipGraph: each replay is a DDIM shape step with ten ancestral layout steps on a parallel branch
         (samplers.sample_layout_and_shape), then the VQ-VAE decode.
@@ -543,11 +603,21 @@ class Sg2ScDiffModel(_SceneModel):
         ``layout_sampler`` / ``layout_steps`` / ``layout_eta``: sampler ('ddpm' | 'ddim'), step count and eta of the LAYOUT loop (None:
         the attributes of ``LayoutDiff``, i.e. the ancestral loop over every trained timestep); with or without gen_shape, and with
         both keep families and the shape keywords.  Each replay of the fused graph then carries n_iter_layout // n_iter_shape layout
-        steps (samplers.sample_layout_and_shape)."""
+        steps (samplers.sample_layout_and_shape).
+
+        ``complete_nodes`` / ``complete_sdfs`` + ``complete_ranges`` or ``complete_masks`` (shape completion, the reference's shape_comp:
+        diffusion_shape/sdfusion_model.py:400-446): the WHOLE given SDF of a listed node is encoded, the latent voxels inside its
+        range (or with mask 1) follow the forward-noised trajectory of that encoding and the others are generated, the node taking
+        part in every step's message passing; its returned row is the decode of the final latent -- the kept region is not pasted
+        back (the reference pastes nothing).  The encoder's receptive field sees the part outside the range too: a caller with a
+        truly partial scan fills it with the truncation value first (postprocess.partial_shape gives ``shape_part``).  Combines with
+        ``keep_nodes`` in ONE plan of the voxel loop (a kept node is an all-ones mask row; its returned row stays the caller's SDF);
+        ``keep_noise`` is the one table of q_sample's draws for both; a node cannot be in both lists."""
         lopts = dict(layout_sampler=layout_sampler, layout_steps=layout_steps, layout_eta=layout_eta)
         self.LayoutDiff.layout_options(**{k[len('layout_'):]: v for k, v in lopts.items()})
         if (keep_nodes is None) != (keep_sdfs is None):
             raise ValueError('keep_nodes and keep_sdfs go together')
+        comp = self.ShapeDiff.check_complete(complete_nodes, complete_sdfs, complete_ranges, complete_masks, keep_nodes, gen_shape)
         if not gen_shape:
             if keep_nodes is not None:
                 raise ValueError('keep_nodes / keep_sdfs keep SHAPES: they need gen_shape=True')
@@ -570,6 +640,11 @@ class Sg2ScDiffModel(_SceneModel):
         if keep_nodes is not None:
             x0, mask, rows, kept = S.keep_inputs(keep_nodes, keep_sdfs, uc.shape[0], sden.device)
             kw.update(x0=x0, mask=mask, keep_noise=keep_noise)
+        if comp is not None:
+            if keep_nodes is None:
+                x0, mask = torch.zeros((uc.shape[0],) + tuple(S.z_shape), device=sden.device), torch.zeros(uc.shape[0])
+            x0, vmask = S.complete_inputs(comp, x0, mask, sden.device)
+            kw.update(x0=x0, mask=vmask, keep_noise=keep_noise)
         if bk:
             kw.update(box_x0=bk['x0'], box_mask=bk['mask'], box_keep_noise=bk['keep_noise'])
         x, z = sample_layout_and_shape(L._denoiser(layout_sampler, layout_steps, layout_eta), sden, obj_embed_, dec_triples, uc, c if need_c else None,
@@ -596,15 +671,16 @@ class Sg2ScDiffModel(_SceneModel):
     def sample(self, dec_objs, dec_triplets, dec_text_feat, dec_rel_feat, gen_shape=False, layout_noise=None,
                shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None,
                keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None, layout_sampler=None,
-               layout_steps=None, layout_eta=None):
-        """EchoScene.py:388-420.  ``keep_nodes`` / ``keep_sdfs`` and ``keep_box_nodes`` / ``keep_boxes`` (keyword-only): see
-        _layout_and_shapes."""
+               layout_steps=None, layout_eta=None, complete_nodes=None, complete_sdfs=None, complete_ranges=None, complete_masks=None):
+        """EchoScene.py:388-420.  ``keep_nodes`` / ``keep_sdfs``, ``keep_box_nodes`` / ``keep_boxes`` and ``complete_nodes`` / ``complete_sdfs`` /
+        ``complete_ranges`` / ``complete_masks`` (keyword-only): see _layout_and_shapes."""
         oe, _, latent_m = self._setup(dec_objs, dec_triplets, dec_text_feat, dec_rel_feat,
                                       dec_objs, dec_triplets, dec_text_feat, dec_rel_feat)
         sdf, boxes = self._layout_and_shapes(gen_shape, dec_objs, dec_triplets, oe, latent_m, layout_noise, shape_noise,
                                              keep_nodes=keep_nodes, keep_sdfs=keep_sdfs, keep_noise=keep_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise,
                                              shape_sampler=shape_sampler, shape_steps=shape_steps,
-                            layout_sampler=layout_sampler, layout_steps=layout_steps, layout_eta=layout_eta)
+                            layout_sampler=layout_sampler, layout_steps=layout_steps, layout_eta=layout_eta,
+                            complete_nodes=complete_nodes, complete_sdfs=complete_sdfs, complete_ranges=complete_ranges, complete_masks=complete_masks)
         return {'shapes': sdf}, boxes
 
     def _edited(self, enc, dec, touched, added, gen_shape, layout_noise, shape_noise, change_rows=None, strict=False, **opts):
@@ -620,21 +696,22 @@ class Sg2ScDiffModel(_SceneModel):
                             dec_text_feat, dec_rel_feat, manipulated_nodes, gen_shape=False, layout_noise=None,
                             shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None,
                             keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None, layout_sampler=None,
-               layout_steps=None, layout_eta=None):
+               layout_steps=None, layout_eta=None, complete_nodes=None, complete_sdfs=None, complete_ranges=None, complete_masks=None):
         """EchoScene.py:422-472.  ``keep_nodes`` / ``keep_sdfs`` (keyword-only): see _layout_and_shapes."""
         return self._edited((enc_objs, enc_triples, enc_text_feat, enc_rel_feat),
                             (dec_objs, dec_triplets, dec_text_feat, dec_rel_feat),
                             list(manipulated_nodes), [], gen_shape, layout_noise, shape_noise,
                             keep_nodes=keep_nodes, keep_sdfs=keep_sdfs, keep_noise=keep_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise,
                             shape_sampler=shape_sampler, shape_steps=shape_steps,
-                            layout_sampler=layout_sampler, layout_steps=layout_steps, layout_eta=layout_eta)
+                            layout_sampler=layout_sampler, layout_steps=layout_steps, layout_eta=layout_eta,
+                            complete_nodes=complete_nodes, complete_sdfs=complete_sdfs, complete_ranges=complete_ranges, complete_masks=complete_masks)
 
     @torch.no_grad()
     def sample_with_additions(self, enc_objs, enc_triples, enc_text_feat, enc_rel_feat, dec_objs, dec_triplets,
                               dec_text_feat, dec_rel_feat, missing_nodes, gen_shape=False, layout_noise=None,
                               shape_noise=None, *, keep_nodes=None, keep_sdfs=None, keep_noise=None, keep_box_nodes=None,
                               keep_boxes=None, keep_box_noise=None, shape_sampler=None, shape_steps=None, layout_sampler=None,
-               layout_steps=None, layout_eta=None):
+               layout_steps=None, layout_eta=None, complete_nodes=None, complete_sdfs=None, complete_ranges=None, complete_masks=None):
         """EchoScene.py:474-532: zero rows inserted at ``missing_nodes[i] + i``; note the reference draws the
         change noise for rows listed in ``missing_nodes`` (:489-494) but splices / masks ``nodes_added``."""
         added = [m + i for i, m in enumerate(missing_nodes)]
@@ -643,7 +720,8 @@ class Sg2ScDiffModel(_SceneModel):
                             added, added, gen_shape, layout_noise, shape_noise, change_rows=list(missing_nodes), strict=True,
                             keep_nodes=keep_nodes, keep_sdfs=keep_sdfs, keep_noise=keep_noise, keep_box_nodes=keep_box_nodes, keep_boxes=keep_boxes, keep_box_noise=keep_box_noise,
                             shape_sampler=shape_sampler, shape_steps=shape_steps,
-                            layout_sampler=layout_sampler, layout_steps=layout_steps, layout_eta=layout_eta)
+                            layout_sampler=layout_sampler, layout_steps=layout_steps, layout_eta=layout_eta,
+                            complete_nodes=complete_nodes, complete_sdfs=complete_sdfs, complete_ranges=complete_ranges, complete_masks=complete_masks)
 
     def state_dict(self, epoch=None, counter=None, **kw):
         """EchoScene.py:534-543 when called with (epoch, counter); plain nn.Module.state_dict otherwise."""
@@ -768,9 +846,13 @@ class SGDiff(nn.Module):
         self.diff.invalidate()
         return r
 
-    def _no_keep_without_shapes(self, kw):
+    def _no_keep_without_shapes(self, kw, gen_shape=True):
         if self.type_ == 'echolayout' and any(kw.get(k) is not None for k in ('keep_nodes', 'keep_sdfs', 'keep_noise')):
             raise ValueError("keep_nodes / keep_sdfs keep SHAPES; an 'echolayout' model has no shape branch")
+        if self.type_ == 'echolayout' and any(kw.get(k) is not None for k in _COMPLETE_OPTS):
+            raise ValueError("complete_nodes / complete_sdfs complete SHAPES; an 'echolayout' model has no shape branch")
+        if self.type_ == 'echoscene':       # the completion keywords are checked before any device work, as the layout keywords below
+            self.diff.ShapeDiff.check_complete(*(kw.get(k) for k in _COMPLETE_OPTS), keep_nodes=kw.get('keep_nodes'), gen_shape=gen_shape)
         if self.type_ == 'echolayout' and any(kw.get(k) is not None for k in ('shape_sampler', 'shape_steps')):
             raise ValueError("shape_sampler / shape_steps choose the sampler of the SHAPE loop; an 'echolayout' model has no shape branch")
         # the layout keywords are checked before any device work (an unknown sampler, layout_steps / layout_eta without 'ddim', ...)
@@ -801,8 +883,16 @@ class SGDiff(nn.Module):
         the trained timesteps (eta 0: deterministic; eta scales the per-step noise), e.g. ``layout_steps=100`` -- a tenth of the
         launches of the layout loop.  ``layout_noise`` is then f32 [n_iter + 1, O, 8] and ``keep_box_noise`` f32 [n_iter, O, 8] over the
         schedule's iterations.  ``layout_steps`` / ``layout_eta`` with 'ddpm', or an unknown name, is a ValueError.  They combine with
-        ``keep_box_nodes`` / ``keep_boxes`` and with the shape keywords; also on the two editing calls."""
-        self._no_keep_without_shapes(noise)
+        ``keep_box_nodes`` / ``keep_boxes`` and with the shape keywords; also on the two editing calls.
+        ``complete_nodes`` + ``complete_sdfs`` f32 [K,1,64,64,64] + exactly one of ``complete_ranges`` (K dicts {'x': (a, b), 'y': ...,
+        'z': ...} in [-1, 1], the xyz_dict of the reference's get_partial_shape) and ``complete_masks`` f32 [K,1,16,16,16] of zeros and
+        ones in latent space (keyword-only, with gen_shape=True): shape completion, the reference's shape_comp -- the whole given SDF is
+        encoded, the latent voxels inside the range keep following it and the rest of the shape is generated in the context of the
+        scene; the returned row is the decode of the final latent (no paste-back).  The encoder sees the part outside the range too:
+        a truly partial scan is filled with 0.2 there first (postprocess.partial_shape).  Combines with ``keep_nodes`` (one voxel plan,
+        ``keep_noise`` the one table for both; a node in both lists is a ValueError), ``shape_sampler='plms'``, ``shape_steps``,
+        ``keep_box_nodes`` and the layout keywords; also on the two editing calls."""
+        self._no_keep_without_shapes(noise, gen_shape)
         if self.type_ == 'echolayout':
             return self.diff.sampleBoxes(dec_objs, dec_triplets, encoded_dec_text_feat, encoded_dec_rel_feat,
                                          layout_noise=noise.get('layout_noise'), **self._box_kw(noise))
@@ -813,7 +903,7 @@ class SGDiff(nn.Module):
     def sample_boxes_and_shape_with_changes(self, enc_objs, enc_triples, encoded_enc_text_feat, encoded_enc_rel_feat,
                                             dec_objs, dec_triples, encoded_dec_text_feat, encoded_dec_rel_feat,
                                             manipulated_nodes, gen_shape=False, **noise):
-        self._no_keep_without_shapes(noise)
+        self._no_keep_without_shapes(noise, gen_shape)
         if self.type_ == 'echolayout':
             return self.diff.sampleBoxes_with_changes(enc_objs, enc_triples, encoded_enc_text_feat, encoded_enc_rel_feat,
                                                       dec_objs, dec_triples, encoded_dec_text_feat, encoded_dec_rel_feat,
@@ -826,7 +916,7 @@ class SGDiff(nn.Module):
     def sample_boxes_and_shape_with_additions(self, enc_objs, enc_triples, encoded_enc_text_feat, encoded_enc_rel_feat,
                                               dec_objs, dec_triples, encoded_dec_text_feat, encoded_dec_rel_feat,
                                               missing_nodes, gen_shape=False, **noise):
-        self._no_keep_without_shapes(noise)
+        self._no_keep_without_shapes(noise, gen_shape)
         if self.type_ == 'echolayout':
             keep, layout_dict = self.diff.sampleBoxes_with_additions(
                 enc_objs, enc_triples, encoded_enc_text_feat, encoded_enc_rel_feat, dec_objs, dec_triples,

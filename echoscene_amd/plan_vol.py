@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import hip
-from .hip import ConvArgs, GNArgs, LNArgs, AttnArgs, GegluArgs, ToClArgs, StemArgs, BlendArgs, ConvC1Args, Op
+from .hip import ConvArgs, GNArgs, LNArgs, AttnArgs, GegluArgs, ToClArgs, StemArgs, BlendArgs, BlendVoxArgs, ConvC1Args, Op
 from .plan import (Builder, PackedLinear, GCNWeights, View, seg, emit_gcn, own, mm64)
 
 
@@ -550,6 +550,18 @@ class VolBuilderMixin:
         self.keep += [x0, mask, noise, tab]
         return self._push(hip.OP_DDIM_BLEND, 'blend', a)
 
+    def blend_vox(self, x, x0, mask, noise, tab, step):
+        """masked-DDIM blend with a mask per latent voxel (es_ddim_blend_vox: shape completion) of the latents x [O, C, ...] with the
+        forward-noised x0 where mask [O, V] is 1 (V = voxels of one channel; the C channels share it); noise [S, O * C * V], tab [S, 2]"""
+        a = BlendVoxArgs()
+        a.x, a.x0, a.mask, a.noise = x.data_ptr(), x0.data_ptr(), mask.data_ptr(), noise.data_ptr()
+        a.O, a.C, a.V = x.shape[0], x.shape[1], x[0, 0].numel()
+        assert tuple(mask.shape) == (a.O, a.V), (tuple(mask.shape), a.O, a.V)
+        a.noise_stride = noise.shape[1]
+        a.tab, a.step = tab.data_ptr(), step.data_ptr()
+        self.keep += [x0, mask, noise, tab]
+        return self._push(hip.OP_DDIM_BLEND_VOX, 'blend_vox', a)
+
     def plms(self, kind, x, eps, coef, step, ring, xsave, inc_step=True, push=True):
         """a PLMS sampler op (es_plms_update / es_plms_first_a / es_plms_first_b, ``kind`` = hip.OP_PLMS*): x [O, ...], eps a tensor or
         a (slab) View, coef the DDIM table [S, 4], ring [3, n] the last three eps, xsave [n] (first iteration only).  ``push=False``: the op is returned, not
@@ -875,7 +887,7 @@ def emit_unet3d_step(b, w, g, x, uc_dev, temb, step, eps_out, dims=(16, 16, 16),
     return objbuf
 
 
-for _n in ('_push', 'conv', '_conv32', 'split3', 'conv_gn_intermediate', '_rowgroup_producer', '_rowgroup_stats', 'groupnorm', 'layernorm', 'attention', 'geglu', 'to_cl', 'stem', 'conv_c1', 'blend', 'plms'):
+for _n in ('_push', 'conv', '_conv32', 'split3', 'conv_gn_intermediate', '_rowgroup_producer', '_rowgroup_stats', 'groupnorm', 'layernorm', 'attention', 'geglu', 'to_cl', 'stem', 'conv_c1', 'blend', 'blend_vox', 'plms'):
     setattr(Builder, _n, getattr(VolBuilderMixin, _n))
 
 

@@ -66,6 +66,69 @@ def postprocess_sincos2arctan(sincos):
     return out
 
 
+def range_bounds(ranges, n):
+    """The integer bounds of get_partial_shape (diffusion_shape/diff_utils/demo_util.py:183-201, :232-239) for a grid of ``n`` cells
+    per axis: ``ranges`` = K dicts {'x': (a, b), 'y': (a, b), 'z': (a, b)} in [-1, 1] (the reference's xyz_dict; one dict is K = 1) ->
+    int32 [K, 6] = (st, ed) of 'x', 'y', 'z' -- dims 2, 3 and 4 of a [B, 1, n, n, n] tensor.  The reference's rule in Python floats, as
+    it is written there: each end clamped to [-1, 1], then int((v - (-1)) / 2 * n).  A voxel is inside when st <= index < ed on all
+    three axes; st >= ed on any axis selects nothing.  Host only."""
+    if isinstance(ranges, dict):
+        ranges = [ranges]
+    out = np.zeros((len(ranges), 6), np.int32)
+    for k, r in enumerate(ranges):
+        if not isinstance(r, dict) or set(r) != {'x', 'y', 'z'}:
+            raise ValueError("range_bounds: entry %d must be a dict with the keys 'x', 'y', 'z' (each a (min, max) pair), got %r" % (k, r))
+        for a, key in enumerate(('x', 'y', 'z')):
+            lo, hi = r[key]
+            lo, hi = max(-1, lo), min(1, hi)
+            out[k, 2 * a] = int((lo - (-1)) / 2 * n)
+            out[k, 2 * a + 1] = int((hi - (-1)) / 2 * n)
+    return out
+
+
+def latent_range_mask(ranges, zdims=(16, 16, 16), device=None):
+    """``z_mask`` of get_partial_shape (demo_util.py:229-252) for K ranges: f32 [K, 1, *zdims] on ``device``, 1 on the latent voxels
+    inside the range -- what ``complete_masks=`` of the scene calls and a per-voxel ``mask=`` of ShapeDenoiser.sample take.  The
+    reference assumes a cubic grid; so does this (es_range_mask)."""
+    zdims = tuple(int(d) for d in zdims)
+    if len(zdims) != 3 or len(set(zdims)) != 1:
+        raise ValueError('latent_range_mask: zdims must be a cubic grid (n, n, n), got %r' % (zdims,))
+    device = torch.device('cuda') if device is None else torch.device(device)
+    b = torch.from_numpy(range_bounds(ranges, zdims[0])).to(device)
+    K = b.shape[0]
+    out = torch.empty(K, 1, *zdims, dtype=torch.float32, device=device)
+    if K:
+        hip.check(hip.lib().es_range_mask(C.c_void_p(b.data_ptr()), K, zdims[0], zdims[1], zdims[2], C.c_void_p(out.data_ptr()),
+                                          hip.current_stream()), 'es_range_mask')
+    return out
+
+
+def partial_shape(sdf, ranges, fill=0.2, zdims=(16, 16, 16)):
+    """get_partial_shape (demo_util.py:172-254) for SDF grids [K, 1, n, n, n] on the device, one range per grid (``ranges`` as
+    range_bounds): a dict of ``shape_part`` (the SDF inside the range, ``fill`` -- the truncation value -- outside), ``shape_missing``
+    (the complement), ``shape_mask`` (bool [K, 1, n, n, n]) and ``z_mask`` (latent_range_mask at ``zdims``), all on the device.
+    ``shape_part`` is what a caller with a truly partial scan hands to ``complete_sdfs=``: the encoder then sees the truncation value,
+    not the shape, outside the range."""
+    x = sdf
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 5 and x.shape[1] == 1
+            and x.shape[2] == x.shape[3] == x.shape[4]):
+        raise ValueError('partial_shape: expects a float32 CUDA tensor [K, 1, n, n, n]')
+    x = x.contiguous()
+    K, n = x.shape[0], x.shape[2]
+    bounds = range_bounds(ranges, n)
+    if bounds.shape[0] != K:
+        raise ValueError('partial_shape: %d ranges for %d SDFs (one range per grid)' % (bounds.shape[0], K))
+    b = torch.from_numpy(bounds).to(x.device)
+    part, missing = torch.empty_like(x), torch.empty_like(x)
+    smask = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    if K:
+        hip.check(hip.lib().es_partial_shape(C.c_void_p(x.data_ptr()), C.c_void_p(b.data_ptr()), K, n, float(fill),
+                                             C.c_void_p(part.data_ptr()), C.c_void_p(missing.data_ptr()), C.c_void_p(smask.data_ptr()),
+                                             hip.current_stream()), 'es_partial_shape')
+    return {'shape_part': part, 'shape_missing': missing, 'shape_mask': smask.bool(),
+            'z_mask': latent_range_mask(ranges, zdims, x.device)}
+
+
 _MC_TABLE = {}
 
 

@@ -100,19 +100,23 @@ def emit_layout_step(b, w, g, obj_embed, temb, tables, T, coef=None, keep_tab=No
 
 
 def emit_shape_step(b, w, g, uc, temb, tables, coef, keep_tab, S, z_shape, lo, hi, c_local=None, gather_rows=None, keep=False,
-                    plms=False, step_noise=False):
+                    plms=False, step_noise=False, keep_vox=False):
     """The shape loop step on ``b`` for the objects lo:hi of the graph: the blend of the masked loop (``keep``; the reference blends
     before p_sample_ddim, samplers/ddim.py:160-163: the denoiser -- conv-pool stem and shape GCN included -- reads the kept objects'
     forward-noised latents), one UNet3D evaluation, then the sampler's tail: es_ddim_update, the same with the per-step draws
     (``step_noise``: eta != 0), or es_plms_update (``plms``; its two first-iteration ops are returned as ``first_ops``, not appended).
+    ``keep_vox``: the voxel form of the masked loop (shape completion) -- ``mask`` is [Ol, V], one value per latent voxel, and the one
+    op in front of the denoiser is es_ddim_blend_vox instead of es_ddim_blend; everything else is the ``keep`` step.
     Sharding hints travel as attributes of ``b`` (shard_block, force_exchange, o_hint), as the results of emit_unet3d_step do."""
+    keep = bool(keep or keep_vox)
     x = b.buf(hi - lo, *z_shape)
     eps = b.buf(hi - lo, *z_shape)
     step = b.buf(1, dtype=torch.int32, zero=True)
     out = dict(x=x, eps=eps, step=step, n_blend=1 if keep else 0, first_ops=(None, None))
     if keep:
-        out.update(x0=b.buf(hi - lo, *z_shape, zero=True), mask=b.buf(hi - lo, zero=True), knoise=b.buf(S, x.numel(), zero=True))
-        b.blend(x, out['x0'], out['mask'], out['knoise'], keep_tab, step)
+        mshape = (hi - lo, math.prod(int(d) for d in z_shape[1:])) if keep_vox else (hi - lo,)
+        out.update(x0=b.buf(hi - lo, *z_shape, zero=True), mask=b.buf(*mshape, zero=True), knoise=b.buf(S, x.numel(), zero=True))
+        (b.blend_vox if keep_vox else b.blend)(x, out['x0'], out['mask'], out['knoise'], keep_tab, step)
     ucd = b.dev(uc)
     b.xc = b.cdev = b.pred_rows = None                   # (results emit_unet3d_step leaves on the Builder; not every variant has these)
     out['objbuf'] = emit_unet3d_step(b, w, g, x, ucd, temb, step, eps, dims=z_shape[1:], lo=lo, hi=hi, c_dev=c_local, tables=tables,
@@ -161,15 +165,33 @@ def _check_keep_pair(x0, mask, keep_noise, loop, arg=''):
         raise ValueError('%skeep_noise without a %smask' % (arg, arg))
 
 
-def _check_mask(x0, mask, shape, loop, form, unit):
-    """mask [O] of zeros and ones and x0 of ``shape`` = [O, ...] for the masked loop ``loop``; returns (x0, mask f32 [O])"""
-    mask = torch.as_tensor(mask, dtype=torch.float32).reshape(-1)
+def _check_mask(x0, mask, shape, loop, form, unit, per=1):
+    """mask [O] of zeros and ones and x0 of ``shape`` = [O, ...] for the masked loop ``loop``; returns (x0, mask f32 [O]).
+    ``per`` > 1: a mask of ``per`` values for each object, returned as it is, [O, per]"""
+    mask = torch.as_tensor(mask, dtype=torch.float32)
+    mask = mask.reshape(-1) if per == 1 else mask
     x0 = torch.as_tensor(x0)
-    if mask.numel() != shape[0] or tuple(x0.shape) != tuple(shape):
+    if mask.numel() != shape[0] * per or tuple(x0.shape) != tuple(shape):
         raise ValueError('%s: x0 must be %s = %s and mask [O]; got %s and %d entries' % (loop, form, tuple(shape), tuple(x0.shape), mask.numel()))
     if not bool(((mask == 0) | (mask == 1)).all()):
         raise ValueError('%s: the mask is per %s, 0 (generate) or 1 (keep)' % (loop, unit))
     return x0, mask
+
+
+def _check_shape_mask(x0, mask, O, z_shape):
+    """mask and x0 of the masked shape loop -> (x0, mask f32, vox).  The mask is per object -- [O] -> f32 [O], vox False -- or per latent
+    voxel, shared by the channels -- [O, 1, D, H, W] or [O, D, H, W] -> f32 [O, D * H * W], vox True.  Anything else (a per-channel
+    mask [O, C, D, H, W] too) is refused."""
+    z_shape = tuple(int(d) for d in z_shape)
+    zd = z_shape[1:]
+    m = torch.as_tensor(mask, dtype=torch.float32)
+    if tuple(m.shape) in ((O, 1) + zd, (O,) + zd, (O, math.prod(zd))):          # (the last: the flattened form the plan's buffer has)
+        return _check_mask(x0, m.reshape(O, -1), (O,) + z_shape, 'masked DDIM', '[O, C, D, H, W]', 'voxel', per=math.prod(zd)) + (True,)
+    if m.numel() != O:
+        raise ValueError('masked DDIM: the mask is per object, [O] = [%d], or per latent voxel, [O, 1, D, H, W] / [O, D, H, W] with '
+                         '(D, H, W) = %s -- one value for all channels; got %s (a mask per channel is not supported)'
+                         % (O, zd, tuple(m.shape)))
+    return _check_mask(x0, m, (O,) + z_shape, 'masked DDIM', '[O, C, D, H, W]', 'object') + (False,)
 
 
 class LayoutDenoiser:
@@ -471,8 +493,8 @@ class ShapeDenoiser:
             b.o_hint = -CANON_OBJECTS   # split-K / partial-sum tiling of the reference shard -> bit-identical latents at every world size
         plms = sampler == 'plms'
         bufs = emit_shape_step(b, self.w, g, uc, self.temb, self.tables, self.coef, self.keep_tab, self.S, self.z_shape, lo, hi,
-                               c_local=None if c is None else c[lo:hi], gather_rows=block * self.world, keep=keep, plms=plms,
-                               step_noise=self.ddim_eta != 0.0)
+                               c_local=None if c is None else c[lo:hi], gather_rows=block * self.world, keep=bool(keep), plms=plms,
+                               step_noise=self.ddim_eta != 0.0, keep_vox=keep == 'vox')
         ops = compose_step_plans(b.ops, bufs.pop('n_blend'), bufs.pop('split'), bufs.pop('n_eps_ops'), *bufs.pop('first_ops'), plms=plms,
                                  sharded=(self.world > 1 or self.force_exchange) and self.w.mp)
         st = new_state(lo=lo, hi=hi, O=O, g=g, sig=sig, sampler=sampler, **bufs)
@@ -491,7 +513,9 @@ class ShapeDenoiser:
         once per iteration, before p_sample_plms, plms.py:154-159).  The 'ddim' plans are, op for op, what they have always been.
         ``keep=True``: the plan of the MASKED loop -- one more op, the blend (es_ddim_blend), in front of the step's denoiser ops,
         and its three inputs: ``x0`` [Ol, C,D,H,W], ``mask`` [Ol], ``knoise`` [S, Ol * latent].  A plan of its own (another cache key):
-        without a mask the plan is, op for op, what it has always been."""
+        without a mask the plan is, op for op, what it has always been.
+        ``keep='vox'``: the voxel form of the masked loop (shape completion) -- the same plan with es_ddim_blend_vox for the blend and
+        ``mask`` [Ol, D * H * W]; again a cache key of its own ('keepvox'), so the two plans above stay what they are."""
         uc = uc.reshape(uc.shape[0], -1)
         O = uc.shape[0]
         concat = self.w.concat
@@ -504,7 +528,7 @@ class ShapeDenoiser:
             c = None
         cap = _cap(triples.shape[0])
         sampler = self._sampler_of(sampler)
-        key = ((O, cap, 'keep') if keep else (O, cap)) + (('plms',) if sampler == 'plms' else ())
+        key = ((O, cap, 'keepvox' if keep == 'vox' else 'keep') if keep else (O, cap)) + (('plms',) if sampler == 'plms' else ())
         sig = hash(triples.detach().cpu().numpy().tobytes())
         st = self._plans.get(key)
         if st is None:
@@ -561,7 +585,9 @@ class ShapeDenoiser:
 
     def save_model(self, path, uc, triples, c=None, keep=False):
         """The DDIM loop of this scene (single GPU) as a model file for hosts without Python (es_model_load + es_shape_sample).
-        ``keep=True``: the masked loop; the host fills the regions "x0" [O,C,D,H,W], "mask" [O] and "keep_noise" [S, O x latent]."""
+        ``keep=True``: the masked loop; the host fills the regions "x0" [O,C,D,H,W], "mask" [O] and "keep_noise" [S, O x latent].
+        ``keep='vox'``: the voxel form of the masked loop (shape completion); the region "mask" is then O * V floats, one per latent
+        voxel ([O, D * H * W]), filled by the host in the same way."""
         from .plan import save_model
         if self.sampler == 'plms':
             raise NotImplementedError("model files hold the DDIM loop only (es_shape_sample); sampler='plms' has no C host yet")
@@ -670,7 +696,7 @@ class ShapeDenoiser:
     def _fill_keep(self, st, x0, mask, keep_noise):
         """inputs of the masked loop into the plan's buffers (this rank's objects lo:hi of the scene's)"""
         O, lo, hi = st['O'], st['lo'], st['hi']
-        x0, mask = _check_mask(x0, mask, (O,) + self.z_shape, 'masked DDIM', '[O, C, D, H, W]', 'object')
+        x0, mask, _ = _check_shape_mask(x0, mask, O, self.z_shape)         # (per object [O] or per voxel [O, V]: rows lo:hi either way)
         if keep_noise is not None and (keep_noise.shape[0] < self.S or keep_noise[0].numel() != O * self.per):
             raise ValueError('masked DDIM: keep_noise must be [S, O, C, D, H, W]')
         if not st['empty']:
@@ -684,7 +710,11 @@ class ShapeDenoiser:
         the keep table [S, O * latent], then ``noise1`` [1, C, D, H, W], then ``step_noise`` [S, O * latent] (eta != 0 only); sharded, the
         two tables are those of the whole scene on every rank (_fill_table)."""
         _check_keep_pair(x0, mask, keep_noise, 'masked DDIM')
-        st = self._plan_for(uc, triples, c, keep=mask is not None, sampler=sampler)
+        keep = False
+        if mask is not None:
+            x0, mask, vox = _check_shape_mask(x0, mask, uc.shape[0], self.z_shape)
+            keep = 'vox' if vox else True
+        st = self._plan_for(uc, triples, c, keep=keep, sampler=sampler)
         if mask is not None:
             self._fill_keep(st, x0, mask, keep_noise)
         if noise1 is None:
@@ -705,8 +735,14 @@ class ShapeDenoiser:
         generated: ``mask`` [O] with 1 = keep, 0 = generate, ``x0`` f32[O,C,D,H,W] the kept objects' latents (rows with mask 0 are not
         read; ``VQEncoder.encode_no_quant`` of their SDFs) and ``keep_noise`` f32[S,O,C,D,H,W] the draws of q_sample (None: drawn on the
         device).  Before every step the kept rows are set to ``sqrt_ac[t] * x0 + sqrt(1 - ac)[t] * keep_noise[step]``; they take part
-        in the step's echo message passing like every other node.  The reference accepts any tensor as mask; this one is per object,
-        which is what editing a scene needs.  ``mask=None``: the loop and its plan are what they are without this feature.
+        in the step's echo message passing like every other node.  ``mask=None``: the loop and its plan are what they are without this
+        feature.
+        Shape completion (``shape_comp``, diffusion_shape/sdfusion_model.py:400-446): ``mask`` may also be per latent VOXEL --
+        [O, 1, D, H, W] or [O, D, H, W] of zeros and ones, one value for the C channels, the ``z_mask`` of get_partial_shape
+        (postprocess.latent_range_mask) -- with ``x0`` the encoding of the WHOLE given shape: the voxels with mask 1 follow the
+        forward-noised trajectory of ``x0``, the others are generated (es_ddim_blend_vox; a plan of its own).  An all-ones row is a
+        kept object, bit for bit the per-object loop's; an all-zero row a generated one.  The reference accepts any tensor as mask;
+        these two forms are offered, and any other shape -- a mask per channel [O, C, D, H, W] too -- is a ValueError.
         ``sampler``: 'ddim' / 'plms' for this call (None: the denoiser's own).  PLMS: ``n_steps`` counts ITERATIONS -- iteration 0
         evaluates the denoiser twice (improved Euler), so k iterations are k + 1 evaluations; the masked loop blends once per iteration,
         before its first evaluation.

@@ -231,6 +231,33 @@ typedef struct es_blend_args {
     int32_t O, n;           /* objects, floats per object (n % 4 == 0)                          */
 } es_blend_args;
 int es_ddim_blend(const es_blend_args* args, es_stream stream);
+/* Shape completion (csrc/es_complete.hip): the same blend with a mask per latent VOXEL, shared by the C channels -- the z_mask
+ * [B, 1, zH, zW, zD] of get_partial_shape (diffusion_shape/diff_utils/demo_util.py:229-252) that shape_comp hands to the sampler
+ * (diffusion_shape/sdfusion_model.py:400-446):
+ *     x[o, c, v] = mask[o, v] != 0 ? tab[2*step] * x0[o, c, v] + tab[2*step + 1] * noise[step][o, c, v] : x[o, c, v]
+ * The arithmetic of es_ddim_blend (two products, one sum, no fp contraction): an all-ones mask row gives that call's bits.  An element
+ * whose mask is 0 keeps its bits, and what x0 / noise hold there never enters a result (a caller may leave garbage).  `step` is read,
+ * never advanced.  V % 4 == 0, noise_stride % 4 == 0 and >= O * C * V, O <= 65535; x, x0, mask and noise 16-byte aligned. */
+typedef struct es_blend_vox_args {
+    float* x;               /* [O, C, V] latents                                                */
+    const float* x0;        /* [O, C, V] encoded shapes                                         */
+    const float* mask;      /* [O, V] 0 or 1                                                    */
+    const float* noise;     /* [n_steps][noise_stride]: noise + (*step) * noise_stride + (o * C + c) * V + v */
+    int32_t noise_stride;   /* floats between the steps' draws (>= O * C * V)                   */
+    const float* tab;       /* [n_steps][2]                                                     */
+    const int32_t* step;
+    int32_t O, C, V;        /* objects, channels, voxels per channel (V % 4 == 0)               */
+} es_blend_vox_args;
+int es_ddim_blend_vox(const es_blend_vox_args* args, es_stream stream);
+/* mask [K, D*H*W] fp32 (device) = 1 where st <= index < ed on all three axes, else 0; bounds int32 [K, 6] (device) = (st, ed) of the
+ * D, H and W axis -- 'x', 'y', 'z' of the reference's xyz_dict.  st >= ed on any axis gives an all-zero row, as the reference's slice
+ * assignments do (demo_util.py:242-250). */
+int es_range_mask(const int32_t* bounds, int K, int D, int H, int W, float* mask, es_stream stream);
+/* The visualisation half of get_partial_shape (demo_util.py:207-227) on sdf [K, n, n, n] (device fp32), bounds as es_range_mask at the
+ * SDF's resolution: shape_part = the SDF inside the range and `fill` outside (the reference's truncation value 0.2), shape_missing
+ * the complement, shape_mask uint8 1 inside. */
+int es_partial_shape(const float* sdf, const int32_t* bounds, int K, int n, float fill, float* shape_part, float* shape_missing,
+                     uint8_t* shape_mask, es_stream stream);
 /* PLMS sampling of the shape branch (PLMSSampler, diffusion_shape/samplers/plms.py:149-247): pseudo linear multistep on the DDIM schedule,
  * S + 1 denoiser evaluations for S iterations.  coef is the table of es_ddim_update (eta = 0).  ring [3][ring_stride] fp32 holds the eps of
  * the last three iterations, iteration i in slot i % 3; with e = the slab sum of eps (fixed order, as es_ddim_update) and
@@ -563,8 +590,9 @@ enum {
                                                      (20 stays unassigned: es_op_pointer_offsets(20) is pinned to "unknown kind") */
     ES_OP_PLMS = 23, ES_OP_PLMS_FIRST_A = 24, ES_OP_PLMS_FIRST_B = 25,   /* es_plms_update / es_plms_first_a / es_plms_first_b (es_plms_args);
                                                      22 stays unassigned, as 20: es_op_pointer_offsets(22) is pinned to "unknown kind" */
-    ES_OP_DDIM_ROWS = 27                          /* es_ddim_rows_update (es_ddpm_keep_args): the strided DDIM update of the layout loop, masked
+    ES_OP_DDIM_ROWS = 27,                         /* es_ddim_rows_update (es_ddpm_keep_args): the strided DDIM update of the layout loop, masked
                                                      or not.  26 stays unassigned, as 20 and 22 (pinned to "unknown kind") */
+    ES_OP_DDIM_BLEND_VOX = 28                     /* es_ddim_blend_vox (es_blend_vox_args): the masked-DDIM blend with a mask per latent voxel */
 };
 /* Row select: out[r, 0..n) = table[*step, 0..n) for r < rows.  The timestep-dependent but node-independent products of a
  * denoiser (time MLP, all ResBlock emb projections, box/shape time embedding) are tabulated once per schedule
@@ -590,7 +618,7 @@ typedef struct es_op {
         es_linear_args linear; es_update_args update; es_copy_args copy; es_conv_args conv;
         es_gn_args gn; es_ln_args ln; es_attn_args attn; es_geglu_args geglu; es_tocl_args tocl;
         es_stem_args stem; es_vq_args vq; es_rowsel_args rowsel; es_blend_args blend; es_conv_c1_args conv_c1;
-        es_ddpm_keep_args keep; es_plms_args plms;
+        es_ddpm_keep_args keep; es_plms_args plms; es_blend_vox_args blend_vox;
     } u;
 } es_op;
 
@@ -653,6 +681,9 @@ int es_sampler_run(es_plan* plan, int32_t* step, int first_step, int n_steps, in
  * hipMalloc, uploads the contents, rebases the pointers and creates the plan.  Named regions give the caller its I/O:
  *   layout model:  "x" [O,8] state, "noise" [T+1,O,8] (row 0 = x_T, row 1+i = draw of iteration i), "step" int32
  *   shape model :  "x" [O,3,16,16,16] latents, "step" int32
+ *   shape model of the masked loop: also "x0" [O,3,16,16,16], "mask" and "keep_noise" [S, O x latent], filled by the host through
+ *                  es_model_region before es_shape_sample; "mask" is O floats (one per object, es_ddim_blend) or, for the voxel loop
+ *                  (shape completion, es_ddim_blend_vox), O * V floats -- one per latent voxel
  *   layout model saved with keep=True (the masked loop, es_layout_sample_keep): also "x0" [O,8], "mask" [O], "knoise" [T,O,8]
  *                  (q_sample's draws, row i = iteration i) and "ktab" [T,2] (es_ddpm_keep_args.tab)
  *   layout model of a strided DDIM loop (LayoutDenoiser(sampler='ddim'); es_ddim_rows_update is its last op): the same regions with T =
