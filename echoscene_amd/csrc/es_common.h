@@ -7,13 +7,13 @@
 #include <thread>
 #include <vector>
 #include "../../include/echoscene_hip.h"
+#include "es_error.h"
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 
-void es_set_error(const char* fmt, ...);
 // plan executor -> rows launcher: the single-problem rows product the plan runs NEXT (NULL: unknown / not one); consumed by the next
 // rows launch of this thread, whose extra wave prefetches that product's weights (es_rows_x.h)
 struct es_linear_args;
@@ -43,14 +43,6 @@ inline void es_parallel_for(long n, F f) {
         if (_e != hipSuccess) {                                                              \
             es_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
             return 1;                                                                        \
-        }                                                                                    \
-    } while (0)
-
-#define ES_REQUIRE(cond, ...)                                                                \
-    do {                                                                                     \
-        if (!(cond)) {                                                                       \
-            es_set_error(__VA_ARGS__);                                                       \
-            return 2;                                                                        \
         }                                                                                    \
     } while (0)
 

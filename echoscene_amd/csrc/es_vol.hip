@@ -12,7 +12,10 @@
 //   * GroupNorm/SiLU, LayerNorm and GEGLU are bandwidth-trivial side kernels that emit the fp16
 //     operand of the next contraction; bias / time-embedding / residual adds are fused into the
 //     contraction epilogue.
+// Which kernel a conv launch runs on, on which grid and with which split of K is decided in es_conv_route.hip (conv_route(): host
+// arithmetic only, no HIP); this file holds the kernels, their launchers and conv_launch(), which launches what a route names.
 #include "es_common.h"
+#include "es_conv_route.h"
 #include <string>
 #include <algorithm>
 #include <cstdlib>
@@ -27,7 +30,6 @@ __device__ __forceinline__ int f_swz(int row) { return (0x1320 >> (((row >> 2) &
 // ---------------------------------------------------------------------------------------------
 // GroupNorm over channels-last volumes.  Pass 1: per (object, 64-voxel tile) partial sums.
 // ---------------------------------------------------------------------------------------------
-constexpr int GN_VT = 64;
 
 // 4 channels per thread (16-B loads), 64 voxels per workgroup, then channel -> group reduction in LDS.
 __global__ __launch_bounds__(256) void k_gn_partial(const es_gn_args a, float* part, int vt) {
@@ -444,16 +446,9 @@ __global__ __launch_bounds__(256) void k_stem2(const es_stem_args a) {
 //   N = 224 / 448 / 672 (and 3*C, 8*C) are all multiples of 224 at full width; ragged N / M, halo and out-of-volume rows are
 //   out-of-range lanes of the LDS-DMA gather (hardware zero fill) and masked stores.
 // ---------------------------------------------------------------------------------------------
-constexpr int BN = 224, BK = 32, BNP = 256;     // BNP: LDS rows of a weight tile (224 padded to a whole number of 1 KiB pieces per wave;
+constexpr int BK = 32, BNP = 256;               // BNP: LDS rows of a weight tile (BN = 224 columns, es_conv_route.h, padded to a whole number of 1 KiB pieces per wave;
                                                 // the 32 pad rows are zero-filled by out-of-range pieces, never fetched)
 // LDS ring: 3 slots (units ks+1, ks+2 in flight).  A 6-deep ring for lone workgroups measured neutral (round 1).
-
-struct ConvGeom {
-    int O, D, H, W;          // output grid
-    int Hi, Wi;              // input grid (H,W may differ from output for DOWN/UP)
-    int Di;                  // input depth (differs from D for DOWN_DHW / UP_DHW)
-    int lw, lh, ld;          // log2 of W, H, D (output)
-};
 
 
 // Split-K ranges are cut in the SAME places by every conv kernel: in units of one (channel chunk, kd, kh) group = 3 K steps
@@ -2711,14 +2706,6 @@ __global__ __launch_bounds__(256) void k_conv_splitk_reduce_gn(const es_conv_arg
     }
 }
 
-// voxel-tile size of the GroupNorm statistics pass by workgroup count: small problems (few objects per GPU when sharded) get smaller
-// tiles; Oh = the object count of the WHOLE problem (O_hint) so that a shard tiles like the unsharded run
-static inline int gn_voxel_tile(long Oh, int V) {
-    int vt = GN_VT;
-    while (vt > 8 && Oh * ((V + vt - 1) / vt) < 512) vt >>= 1;
-    return vt;
-}
-
 // Row-group sums of es_conv_args.gn_stats_out for the routes whose epilogue does not form them (64- / 128-row tiles, k_linear_ws,
 // split K): one thread per (64-row group, column quad), the summation order of conv_epilogue<STATS_> -- the even rows of the group
 // top to bottom, the odd rows top to bottom, then the two halves -- so that every route leaves the same bits.
@@ -2778,12 +2765,6 @@ __global__ __launch_bounds__(256) void k_gn_finalize_rg(const es_gn_args a, floa
         fin[((long)o * a.groups + g) * 2] = (float)mean;
         fin[((long)o * a.groups + g) * 2 + 1] = (float)(1.0 / sqrt(var + (double)a.eps));
     }
-}
-
-int ilog2_exact(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return (1 << l) == v ? l : -1;
 }
 
 }  // namespace
@@ -2949,51 +2930,6 @@ extern "C" int es_pack_conv_rows_f16(const float* h_w, int N, int CinW, int taps
     return 0;
 }
 
-// ---- Route options of the volume path (round 5: no environment access) -----------------------------------------------------------
-// Everything below decides WHERE an fp32 sum is cut (split-K factors, which kernel forms a GroupNorm's sums) or which kernel family
-// multiplies: it changes the bits of the results.  Until round 4 these were process-environment switches read inside the library: two
-// ranks -- or a process that saves a model file and one that replays it -- with different environments silently disagreed (ADVICE r4,
-// VERDICT r4 #6).  Now they are process-wide options with constant defaults that ONLY an explicit es_vol_set_option() call changes
-// (tests and A/B tools); es_model_save records them in the file and es_model_load refuses a file written under other values.
-// conv_route() below is the only reader of the conv_* options (gn_rg: es_groupnorm_vol).  Next to them it reads three environment switches -- ES_CONV_A3, ES_CONV_LINWS,
-// ES_CONV_N16 -- that move a launch between kernels with the same K order and the same bits; the A/B switches
-// whose variant lost (ES_CONV_NS, ES_CONV_GB, ES_LIN_RING, ES_LIN_NCB_MAX) went with the kernel variants only they reached.
-#ifndef ES_CONV_A3_DEFAULT
-#define ES_CONV_A3_DEFAULT true
-#endif
-struct VolOpt { const char* name; int value; };
-static VolOpt g_vo[] = {
-    {"conv_tile", 0},          // 128: force 128-row tiles
-    {"conv_force256", 0},      // 1: 256-row producer/consumer tiles for any problem size (tests)
-    {"conv_ws", 1},            // 0: k_conv_lean instead of the warp-specialised k_conv_ws
-    {"conv_wssplit", 1},       // 0: small problems on 128- / 64-row tiles instead of 256-row tiles with split K
-    {"conv_wss_target", 256},  // workgroup target of that split
-    {"conv_deep", 1},          // 0: no k_linear_deep for small K-short linear launches
-    {"conv_tinysplit", 1},     // 0: tiny K-short launches without split K
-    {"gn_rg", 1},              // 0: GroupNorm statistics always from a pass over the tensor
-    {"conv_few", 1},           // 0: the few-objects routes of round 6 off (round-5 routing for small problems)
-    {"conv_st_bm", 0},         // tools only: 64 / 128 = every producer/consumer-eligible launch on k_conv_ws tiles of that many rows
-    {"conv_st_np", 4},         // tools only: producer waves of that tile (4; 8 with 128-row tiles)
-    {"conv_st_ns", 3},         // tools only: ring depth of that tile (3; 6 with 64-row tiles, 5 with 128-row tiles and 8 producers)
-    {"conv_kw_ks", 0},         // tools only: 4 / 2 = every eligible launch on k_conv_kw with that many K streams per workgroup
-};
-static int vo(const char* name) {
-    for (const VolOpt& o : g_vo) if (!strcmp(o.name, name)) return o.value;
-    return 0;
-}
-extern "C" int es_vol_set_option(const char* name, int value) {
-    ES_REQUIRE(name != nullptr, "es_vol_set_option: null name");
-    for (VolOpt& o : g_vo) if (!strcmp(o.name, name)) { o.value = value; return 0; }
-    ES_REQUIRE(false, "es_vol_set_option: unknown option '%s'", name);
-}
-// "name=value;name=value;..." of every route option, in a fixed order (what es_model_save records); returns the length needed
-extern "C" int es_vol_options(char* out, int cap) {
-    std::string s;
-    for (const VolOpt& o : g_vo) { s += o.name; s += '='; s += std::to_string(o.value); s += ';'; }
-    if (out && cap > 0) { strncpy(out, s.c_str(), (size_t)cap - 1); out[cap - 1] = 0; }
-    return (int)s.size() + 1;
-}
-
 namespace {
 // The dynamic-LDS limits of a launch site's kernels, raised when the site's function-local static of this type is constructed: once
 // per process (per instantiation of a templated site), thread-safe; err is the first failure.  A site that lists several kernels
@@ -3006,363 +2942,14 @@ struct LdsLimits {
     }
 };
 
-// ---- The route of one es_conv_mfma_f16 launch ------------------------------------------------------------------------------------
-// conv_route() DECIDES (host arithmetic on the arguments, the route options and three environment switches: no HIP call), conv_launch()
-// LAUNCHES what the route names and decides nothing, the planner's queries (es_conv_emits_gn_stats / _gn_part / es_conv_split_of) read
-// a field.  Shard bit-equality, the workspace's slab count and a model file's replay all rest on this rule: keep it in conv_route().
-// The kernel families; k_conv_ws has one value per tile built: rows, consumer waves, producer waves, ring depth
-enum class ConvKernel {
-    none,                      // nothing conv_launch() can launch: a chunked route, or forcing options that name a tile that is not built
-    small_n, small_n_tiled, n16, kw_4_1, kw_2_2, ws_256_8_4_3, ws_64_4_4_3, ws_64_4_4_6, ws_128_4_4_3, ws_128_4_8_3, ws_128_4_8_5, ws3,
-    ws_256_up_fold,            // k_conv_ws_fold: ws_256_8_4_3 of an UP_HW launch on its folded weight image (12 K units per chunk, not 27)
-    linear_ws, linear_deep, lean_256, lean_128, lean_64
-};
-// the enumerators' spelling, in their order (es_conv_kernel_of): a kernel added to the enum is added here
-static const char* const kConvKernelName[] = {
-    "none",
-    "small_n", "small_n_tiled", "n16", "kw_4_1", "kw_2_2", "ws_256_8_4_3", "ws_64_4_4_3", "ws_64_4_4_6", "ws_128_4_4_3", "ws_128_4_8_3", "ws_128_4_8_5", "ws3",
-    "ws_256_up_fold", "linear_ws", "linear_deep", "lean_256", "lean_128", "lean_64"
-};
-static_assert(sizeof(kConvKernelName) / sizeof(kConvKernelName[0]) == (size_t)ConvKernel::lean_64 + 1, "kConvKernelName: one name per ConvKernel value");
-enum class ConvReduce { none, plain, gn_part };      // k_conv_splitk_reduce / k_conv_splitk_reduce_gn behind a launch split over workgroups
-struct ConvRoute {
-    ConvGeom g;
-    int ncdhw;
-    long M;                    // rows of this launch
-    long omax;                 // > 0: over the 2 GiB descriptor limit -- launched in chunks of omax objects, each with a route of its own
-    ConvKernel kernel;
-    dim3 grid;
-    size_t lds;                // small_n / small_n_tiled: dynamic LDS bytes (the other kernels' are constants of their launchers)
-    int S;                     // split of K over workgroups (grid.z; 1: none)
-    int ncb;                   // linear_ws: column tiles a workgroup walks
-    bool upm, geglu;
-    char unbuilt[96];          // kernel == none behind forcing options: what conv_launch() reports
-    bool epi_stats;            // the kernel's epilogue can form the row-group sums of gn_stats_out (es_conv_emits_gn_stats)
-    bool stats;                // ... and does in this launch: gn_stats_out is given
-    bool part_ok;              // the reduction can form a GroupNorm's per-tile partial sums (es_conv_emits_gn_part)
-    ConvReduce reduce;
-    int vt;                    // gn_part: voxel tile of the partial sums
-    bool stats_pass;           // k_rowgroup_stats over the finished output forms gn_stats_out
-    int slabs;                 // es_conv_split_of: fp32 slabs [slabs][M][N] written into the workspace (a chunked launch: in units of the
-                               // whole M x N; 0: a direct kernel, no workspace; for linear_deep the automatic split it stands in for)
-    bool fold_bal;             // ws_256_up_fold on its balanced schedule (k_conv_ws_fold_bal, grid (row tiles, 2); es_conv_fold_balanced)
-};
+// the grid of a route
+dim3 grid_of(const ConvRoute& r) { return dim3(r.gx, r.gy, r.gz); }
 }  // namespace
 
 constexpr int LDS256 = 3 * (256 * BK * 2 + BNP * BK * 2), LDS128 = 3 * (128 * BK * 2 + BNP * BK * 2), LDS64 = 3 * (64 * BK * 2 + BNP * BK * 2);
 constexpr int LDSLIN = LDS256 + 8 * 16 * 116 * 4;            // k_linear_ws: the ring + the epilogue slabs behind it
 constexpr int LDSDEEP = 7 * (64 * BK * 2 + BNP * BK * 2);    // k_linear_deep: 7-slot ring
 constexpr int LDSWS3 = 9 * 16384;                            // k_conv_ws3: 7 B slots + 2 A slots
-
-static int conv_route(const es_conv_args* a, ConvRoute* r) {
-    *r = ConvRoute{};
-    ES_REQUIRE(a->Cin % 32 == 0 && a->Cin > 0, "es_conv_mfma_f16: Cin=%d must be a positive multiple of 32", a->Cin);
-    ES_REQUIRE(a->taps == 27 || a->taps == 1, "es_conv_mfma_f16: taps=%d", a->taps);
-    ES_REQUIRE(!a->a2 || (a->Cin2 % 32 == 0 && a->Cin2 > 0), "es_conv_mfma_f16: Cin2=%d", a->Cin2);
-    ES_REQUIRE(a->out_f32 || a->out_f16, "es_conv_mfma_f16: no output");
-    ES_REQUIRE(a->epilogue == ES_EPI_NONE || (a->epilogue == ES_EPI_GEGLU && a->N % 224 == 0 && a->out_f16 && !a->out_f32 && !a->res &&
-                                              !a->rowvec && !a->a2 && a->bias && a->out_ld >= a->N / 2 && a->out_ld % 8 == 0 && a->splitk <= 1),
-               "es_conv_mfma_f16: GEGLU epilogue needs N %% 224 == 0 (N=%d), bias, f16 output only, no split-K", a->N);
-    ConvGeom& g = r->g;
-    g.O = a->O; g.D = a->D; g.H = a->H; g.W = a->W;
-    g.Hi = a->H; g.Wi = a->W;
-    g.Di = a->D;
-    if (a->mode == ES_CONV_DOWN_HW) { g.Hi = 2 * a->H; g.Wi = 2 * a->W; }
-    ES_REQUIRE(a->mode >= ES_CONV_SAME && a->mode <= ES_CONV_DOWN_DHW_P01, "es_conv_mfma_f16: unknown mode %d", a->mode);
-    if (a->mode == ES_CONV_DOWN_DHW || a->mode == ES_CONV_DOWN_DHW_P01) { g.Hi = 2 * a->H; g.Wi = 2 * a->W; g.Di = 2 * a->D; }
-    if (a->mode == ES_CONV_UP_DHW) g.Di = a->D / 2;
-    if (a->mode == ES_CONV_UP_HW || a->mode == ES_CONV_UP_DHW) { g.Hi = a->H / 2; g.Wi = a->W / 2; }
-    g.lw = ilog2_exact(a->W); g.lh = ilog2_exact(a->H); g.ld = ilog2_exact(a->D);
-    ES_REQUIRE(g.lw >= 0 && g.lh >= 0 && g.ld >= 0, "es_conv_mfma_f16: D,H,W must be powers of two (%d,%d,%d)", a->D, a->H, a->W);
-    const int ncdhw = r->ncdhw = a->out_ld < 0 ? 1 : 0;            // out_ld < 0 selects NCDHW fp32 output [O,N,V]
-    ES_REQUIRE(!ncdhw || (a->out_f32 && !a->res && !a->out_f16), "es_conv_mfma_f16: NCDHW output is fp32-only, no residual");
-    const long M = r->M = (long)a->O * a->D * a->H * a->W;
-    // split-K factors are derived from Mh: the row count of the WHOLE problem when this launch is one shard of it
-    // O_hint < 0 (round 6): the CANONICAL arithmetic of a reference shard of -O_hint objects, whatever the launch's own object count --
-    // every rank of every world size (1 included) cuts K where a shard of that size is cut best, so all of them leave the same bits
-    // and the small shards are the fast ones (until round 5 the reference was the unsharded run and its shards paid 2x)
-    const long Oh = a->O_hint < 0 ? -(long)a->O_hint : (long)(a->O_hint > a->O ? a->O_hint : a->O);
-    const long Mh = Oh * a->D * a->H * a->W;
-    // The kernels address their operands with 31-bit byte offsets from a buffer descriptor.  Larger tensors are processed in
-    // object chunks (every object is independent; O_hint keeps the split-K choice of the whole problem).
-    {
-        const long per_obj_in = (long)g.Di * g.Hi * g.Wi * a->Cin * 2, per_obj_in2 = a->a2 ? (long)a->D * a->H * a->W * a->Cin2 * 2 : 0;
-        const long halo = 4L * ((g.Hi + 1) * g.Wi + 1) * a->Cin;
-        const long lim = (1L << 31) - halo - 1;
-        long omax = a->O;
-        if (per_obj_in > 0) omax = std::min(omax, lim / per_obj_in);
-        if (per_obj_in2 > 0) omax = std::min(omax, lim / per_obj_in2);
-        ES_REQUIRE(omax >= 1, "es_conv_mfma_f16: one object exceeds 2 GiB of input (%ld bytes)", per_obj_in);
-        if (omax < a->O) {
-            // a chunked launch forms no GroupNorm sums in its epilogues; its chunks split K as launches of omax objects do (with
-            // O_hint: as the whole / the reference problem does) and write their slabs into the SAME workspace: report the slab
-            // count in units of the whole launch's M x N (es_conv_split_of: the planner sizes the workspace with it)
-            es_conv_args c = *a;
-            c.O = (int32_t)omax;
-            c.O_hint = a->O_hint < 0 ? a->O_hint : (a->O_hint > a->O ? a->O_hint : a->O);
-            c.gn_stats_out = nullptr; c.gn_part_out = nullptr;
-            ConvRoute rc;
-            if (int err = conv_route(&c, &rc)) return err;
-            r->omax = omax;
-            r->S = rc.S;                                       // (es_conv_kernel_of: the split of a full chunk)
-            r->slabs = (int)((rc.slabs * omax + a->O - 1) / a->O);
-            r->stats_pass = a->gn_stats_out != nullptr;        // (the planes are laid out for the whole tensor: one pass behind the chunks)
-            return 0;
-        }
-    }
-    // N <= 4 with a narrow input (VQ-VAE conv_out 64 -> 1 at 64^3): direct kernel, weights in the rows layout.  Wider
-    // inputs (UNet eps conv 224 -> 3) go through the MFMA tile: 98 % column padding, but the direct kernel's 756
-    // dependent 16-B loads per voxel cost 2.4x (O=32) to 10x (O=4) more than the padded tile.
-    if (a->N <= 4 && a->taps == 27 && a->Cin <= 64) {
-        const size_t lds_t = (size_t)1000 * (a->Cin * 2 + 16) + (size_t)a->N * 27 * a->Cin * 2;
-        const bool tiled = a->D % 8 == 0 && a->H % 8 == 0 && a->W % 8 == 0 && a->Cin % 8 == 0 && lds_t <= 160 * 1024;
-        r->kernel = tiled ? ConvKernel::small_n_tiled : ConvKernel::small_n;
-        r->grid = dim3((unsigned)(tiled ? (long)a->O * (a->D / 8) * (a->H / 8) * (a->W / 8) : (M + 255) / 256));
-        r->lds = tiled ? lds_t : (size_t)a->N * 27 * a->Cin * 2;
-        r->S = 1;
-        return 0;
-    }
-    // N <= 16 from a wide input, NCDHW fp32 output, no fusions (the UNet's output conv): halo'd LDS image + one MFMA column
-    static const char* n16_env = getenv("ES_CONV_N16");           // A/B switch (timing only: same K order, same bits): 0 = off
-    if (a->N <= 16 && a->taps == 27 && a->Cin > 64 && ncdhw && a->mode == ES_CONV_SAME && !a->a2 && !a->res && !a->rowvec &&
-        !a->out_f16 && a->D % 4 == 0 && a->H % 4 == 0 && a->W % 16 == 0 && !(n16_env && atoi(n16_env) == 0) &&
-        (long)a->O * a->D * a->H * a->W * a->Cin * 2 < (1L << 31)) {
-        r->kernel = ConvKernel::n16;
-        r->grid = dim3((unsigned)((long)a->O * (a->D / 4) * (a->H / 4) * (a->W / 16)));
-        r->S = 1;
-        return 0;
-    }
-    const int ntn = (a->N + BN - 1) / BN;
-    // small-M layers (16x4x4 level): 64-row tiles double the number of workgroups (>= 1 per CU)
-    // Tile / split choice by workgroup count (256 CUs x 2 resident workgroups):
-    //   >= 256 workgroups of 256 rows -> 8-wave 256x224 tiles;
-    //   otherwise 128x224 tiles, and when even those give < 512 workgroups (16x4x4 level: M = 8192) K is split
-    //   over S workgroups per tile (fixed-order reduction kernel, deterministic).
-    const long wg256 = ((M + 255) / 256) * ntn, wg128 = ((M + 127) / 128) * ntn;
-    const long hg256 = ((Mh + 255) / 256) * ntn, hg128 = ((Mh + 127) / 128) * ntn;      // the same counts for the whole problem
-    const int nks = a->taps * (a->Cin / 32) + (a->a2 ? a->Cin2 / 32 : 0);
-    const bool want_stats = a->gn_stats_out != nullptr;
-    ES_REQUIRE(!want_stats || ((a->out_f32 || a->out_f16) && !ncdhw && a->N % 4 == 0 && a->out_ld % 4 == 0 && (a->D * a->H * a->W) % 64 == 0 &&
-                               a->epilogue == ES_EPI_NONE),
-               "es_conv_mfma_f16: gn_stats_out needs a channels-last output, N %% 4 == 0 and voxels per object %% 64 == 0");
-    int S = a->splitk;
-    const bool can_split = a->workspace && !ncdhw && a->N % 4 == 0 && a->out_ld % 4 == 0 && (!a->rowvec || a->rowvec_ld % 4 == 0);
-    const bool no256 = vo("conv_tile") == 128;               // (route options: es_vol_set_option, no environment access)
-    const bool force256 = vo("conv_force256") == 1;
-    const bool geglu = a->epilogue == ES_EPI_GEGLU;
-    const bool upm = a->mode == ES_CONV_UP_HW || a->mode == ES_CONV_UP_DHW;
-    // k_conv_ws's epilogue is compiled for vector-aligned channels-last outputs addressed with 32-bit element offsets
-    const bool ws_epilogue_ok = !ncdhw && a->N % 4 == 0 && a->out_ld % 4 == 0 && (!a->rowvec || a->rowvec_ld % 4 == 0) &&
-                                M * (long)a->out_ld < (1L << 30) && M * (long)a->N < (1L << 30) &&
-                                (!a->rowvec || (a->D * a->H * a->W) % 64 == 0);      // a wave's 64 rows in one object: rowvec per wave
-    const bool ws = vo("conv_ws") != 0 && ws_epilogue_ok;
-    // ---- round 6: the few-objects routes (fewer than 256 tiles of 256 rows in the reference problem) --------------------------------
-    // few_ref: what the REFERENCE problem (Mh rows) decides -- 1: a plain split of S over workgroups, 2: S = 4 K streams inside the
-    // workgroup (k_conv_kw, no slabs; the same bits as a plain split of 4).  The launch's own row count only picks the tile that
-    // realises that split: 64- / 128-row producer/consumer tiles, k_conv_kw, or the 256-row tiles when it has >= 256 of them.
-    // Measured at 4 objects per GPU (profiles/r06_tiles_microbench.txt): 3x3x3 launches -5 ... -15 % on 128-row tiles with half the
-    // slabs of the 256-row split; 1x1 launches with 14-105 K units -20 ... -25 % on k_conv_kw; wide 1x1 launches -15 ... -25 % on
-    // 64-row producer/consumer tiles (no split).
-    int few_ref = 0, few_bm = 0;
-    bool few_kw = false;
-    if (vo("conv_few") != 0 && ws && geglu && !upm && a->taps == 1 && a->splitk <= 0 && hg256 < 256 && !no256 && !force256 &&
-        !vo("conv_st_bm") && !vo("conv_kw_ks") && ((M + 127) / 128) * ntn < 320) {
-        // the GEGLU projection of a small problem (never split: its epilogue needs the whole sum): 64-row producer/consumer tiles
-        // instead of the non-specialised 64-row kernel (672 -> 5376 at 16x4x4 with 4 objects)
-        few_ref = 1; S = 1; few_bm = 64;
-    }
-    if (vo("conv_few") != 0 && ws && !geglu && a->splitk < 0 && can_split && hg256 < 256 && !no256 && !force256 &&
-        !vo("conv_st_bm") && !vo("conv_kw_ks")) {
-        const long h128 = ((Mh + 127) / 128) * ntn, h64h = ((Mh + 63) / 64) * ((a->N + 111) / 112);
-        if (a->taps == 27 || nks >= 112) {
-            int s2 = (int)((256 + h128 / 2) / h128);
-            s2 = s2 < 1 ? 1 : (s2 > 8 ? 8 : s2);
-            // (the split that fills the chip best must fit ONE round of workgroups: 96 tiles of 128 rows -- the 16x4x4 level at 16
-            //  objects -- want S = 3 = 288 workgroups; with S = 2 the 256-row tiles' S = 5 is the better use of the chip, 91 against 96 us)
-            const bool one_round = h128 * s2 <= 272;
-            while (s2 > 1 && nks / s2 < 24) --s2;
-            // (very long K on a handful of tiles -- 1344 -> 672 at 16x4x4 with 4 objects -- stays on the 256-row tiles with S = 16;
-            //  an UNSPLIT launch that would leave a quarter of the CUs idle -- 192 tiles of 128 rows: the 16x4x4 level at 32 objects --
-            //  stays on the 256-row tiles with S = 2: the same workgroup count on the tile that moves fewer bytes, 169 against 179 us)
-            if (!(nks >= 800 && h128 * 8 < 256) && one_round && (s2 >= 2 || h128 >= 224)) { few_ref = 1; S = s2; }
-        } else if (a->taps == 1) {
-            if (h64h <= 272 && nks >= 12) { few_ref = 2; S = 4; }          // (one round of 64 x 112 tiles: with 384 of them the 64-row tiles win)
-            else { few_ref = 1; S = 1; }
-        }
-        if (few_ref) {
-            const long l128 = ((M + 127) / 128) * ntn, l64h = ((M + 63) / 64) * ((a->N + 111) / 112);
-            if (wg256 >= 256) few_bm = 0;                                          // enough 256-row tiles: they take the split as it is
-            else if (few_ref == 2 && l64h <= 768) few_kw = true;
-            else if (a->taps == 1 && few_ref == 1 && S == 1) few_bm = l128 >= 320 ? 128 : 64;
-            else few_bm = 128;
-        }
-    }
-    if (S < 0 && !few_ref) {                               // auto
-        S = 1;
-        if (can_split && hg256 < 256 && hg128 < 512) {
-            // ~3 workgroups per CU: enough for the dynamic scheduler to balance the tail, few enough that the epilogue
-            // and the reduction (S slabs of M x N floats) stay small (measured, tools/microbench_small.py: M = 8192
-            // rows best at S = 4, 16384 rows at S = 2-3, 1024-4096 rows at S = 8)
-            S = (int)((768 + hg128 / 2) / hg128);
-            if (S < 1) S = 1;
-            if (S > 8) S = 8;
-            while (S > 1 && nks / S < 24) --S;
-        }
-    }
-    bool split256 = false;
-    if (a->splitk < 0 && !few_ref && S == 1 && can_split && hg256 >= 256) {
-        // tile quantisation: e.g. 384 workgroups of 256 rows on 256 CUs = 2 rounds, the second half empty.  Split K by
-        // the smallest factor that fills the last round (>= 95 %) if the plain launch wastes more than 20 %.
-        const long r1 = (hg256 + 255) / 256;
-        if ((double)hg256 / (double)(r1 * 256) < 0.8)
-            for (int s2 = 2; s2 <= 4; ++s2) {
-                const long w = hg256 * s2;
-                if ((double)w / (double)(((w + 255) / 256) * 256) >= 0.95 && nks / s2 >= 48) { S = s2; split256 = true; break; }
-            }
-    }
-    if (S <= 1 || !can_split) S = 1;
-    ES_REQUIRE(!upm || (!a->a2 && a->taps == 27), "es_conv_mfma_f16: nearest-up modes take 3x3x3 convs without a fused skip");
-    if (force256 && a->splitk < 0 && !split256) S = 1;
-    // Small problems (few objects per GPU: the strong-scaling regime, or the 16x4x4 level): fewer than 256 tiles of 256 rows.  The
-    // 128- / 64-row kernels below stream the weight tile twice / four times per 256 rows and cost 0.9 us per K unit and workgroup
-    // against 0.64 us for a 256-row producer/consumer tile, so keep the 256-row tiles and split K until about one workgroup per
-    // CU runs (A/B ES_CONV_WSSPLIT: shape step 21.44 -> 20.76 ms at 32 objects, 13.69 -> 12.61 / 9.22 -> 8.32 / 6.68 -> 6.27 ms at 16 / 8 / 4).
-    bool ws_split = false;
-    if (ws && !geglu && a->splitk < 0 && !few_ref && can_split && hg256 < 256 && !no256 && !force256 && vo("conv_wssplit") != 0) {
-        // (hg256: the tile count of the WHOLE problem -- a shard with O_hint makes the choice the unsharded run makes, so its
-        //  partial sums are cut in the same places and the results stay bit-identical; it then simply runs fewer workgroups)
-        const long wst = vo("conv_wss_target");              // workgroup target of the split (256 = one round)
-        int s2 = (int)(wst / hg256);
-        const int s2max = Mh * (long)a->N <= (1L << 22) ? 16 : 8;      // workspace contract (echoscene_hip.h): 16 slabs for small outputs
-        if (s2 > s2max) s2 = s2max;
-        while (s2 > 1 && nks / s2 < 24) --s2;
-        if (s2 >= 2 && hg256 * s2 >= 160) { S = s2; ws_split = true; }
-    }
-    // Tiny K-short problems (the transformer linears at <= 8 objects per GPU: e.g. 1024 rows x 672 columns, 21 K units): even the
-    // 64-row tiles give only a few dozen workgroups, each a lone, latency-bound chain of K units (22-30 us for < 1 GFLOP).
-    // Split K over 64-row tiles until about one workgroup per CU runs (>= 5 units per split).
-    // ... round 4: such launches go to k_linear_deep (7-slot ring issued at entry, no split, no reduction kernel) when they are plain
-    // linears of at most ONE round of 64-row tiles (140 KB of LDS = one workgroup per CU: with more tiles than CUs the 3-slot kernel's two
-    // workgroups per CU win; stand-alone at 4 objects: 448 -> 448 19.7 -> 12.5 us, 672 -> 2016 21.4 -> 13.8, but 448 -> 1344 with 384
-    // tiles 16.7 -> 21.3); the split below remains for the shapes it does not take (fused skip phase, 27 taps, more tiles)
-    bool deep = false;
-    {
-        const long hg64 = ((Mh + 63) / 64) * ntn;
-        deep = !ws_split && !few_ref && a->splitk <= 0 && !force256 && !no256 && hg256 < 256 && hg64 <= 256 && a->taps == 1 && !a->a2 && a->mode == ES_CONV_SAME &&
-               nks >= 4 && nks <= 28 && !ncdhw && M * (long)a->Cin * 2 < (1L << 31) && vo("conv_deep") != 0;
-    }
-    bool tiny_split = false;
-    {
-        const long hg64 = ((Mh + 63) / 64) * ntn;
-        if (!deep && !ws_split && !few_ref && a->splitk < 0 && can_split && !force256 && hg256 < 256 && hg128 < 128 && hg64 < 256 && nks >= 10 &&
-            vo("conv_tinysplit") != 0) {
-            int s3 = (int)((256 + hg64 - 1) / hg64);
-            const int s3max = Mh * (long)a->N <= (1L << 22) ? 16 : 8;
-            if (s3 > s3max) s3 = s3max;
-            if (s3 > nks / 5) s3 = nks / 5;
-            if (s3 >= 2) { S = s3; tiny_split = true; }
-        }
-    }
-    // tools: every eligible launch on the small producer/consumer tiles (split K as the caller says, 1 when it says nothing)
-    const int kw_ks = ws && (!geglu || !upm) ? vo("conv_kw_ks") : 0;
-    const int st_bm = kw_ks ? 64 : (ws && (!geglu || !upm) ? vo("conv_st_bm") : 0);
-    if (st_bm) {
-        deep = tiny_split = ws_split = split256 = false;
-        S = a->splitk > 1 && can_split && !geglu ? a->splitk : 1;
-    }
-    const bool few_small = few_ref && (few_kw || few_bm);      // a few-objects launch on its own kernels (not the 256-row tiles)
-    const bool route256 = !st_bm && !few_small && (wg256 >= 256 || force256 || ws_split) && (S == 1 || split256 || ws_split || wg256 >= 256) && !no256 && !tiny_split && !deep;
-    // 1x1 / linear launches with several column tiles: one workgroup walks NCB column tiles of its row tile (k_linear_ws)
-    static const char* lin_env = getenv("ES_CONV_LINWS");        // A/B switch: 0 = off
-    int ncb = 1;
-    if (route256 && ws && a->taps == 1 && !a->a2 && a->mode == ES_CONV_SAME && S == 1 && ntn >= 2 && !(lin_env && atoi(lin_env) == 0)) {
-        static const int cand[5] = {8, 6, 4, 3, 2};
-        for (int k = 0; k < 5; ++k)
-            if (ntn % cand[k] == 0 && ((M + 255) / 256) * (ntn / cand[k]) >= 256) { ncb = cand[k]; break; }
-    }
-    // the producer/consumer 256-row kernel forms the row-group sums of gn_stats_out in its epilogue; every other route runs
-    // k_rowgroup_stats over the finished output
-    const bool epi_stats = (route256 || st_bm == 128 || (few_small && few_bm == 128)) && ncb == 1 && ws && !geglu && S == 1 && (a->out_f32 || a->out_f16) && a->N % 4 == 0 && a->out_ld % 4 == 0 &&
-                           (a->D * a->H * a->W) % 64 == 0;
-    // a split launch can form the next GroupNorm's per-tile partial sums in its reduction kernel (gn_part_out)
-    // (the few-objects routes: from the REFERENCE problem's decision -- K streams inside the workgroup have no reduction launch,
-    //  whatever kernel realises the split in this launch)
-    const bool part_ok = S > 1 && !deep && few_ref != 2 && a->out_f32 && !ncdhw && a->N % 4 == 0 && a->N <= 2048 && a->out_ld == a->N && a->gn_part_groups > 0 &&
-                         a->gn_part_groups <= 64 && a->N % a->gn_part_groups == 0;
-    r->upm = upm; r->geglu = geglu; r->ncb = ncb;
-    r->epi_stats = epi_stats; r->part_ok = part_ok;
-    r->stats = want_stats && epi_stats;
-    r->stats_pass = want_stats && !epi_stats;      // (every kernel chosen below under epi_stats has the epilogue that forms the sums)
-    r->slabs = few_kw ? 1 : S;
-    // ---- the kernel that realises the decision, and its grid ------------------------------------------------------------------------
-    const unsigned uy = (unsigned)ntn;
-    if (few_kw) {
-        S = 1;                                                 // (the four K ranges meet in LDS: no slabs, no reduction launch)
-        r->kernel = ConvKernel::kw_4_1;
-        r->grid = dim3((unsigned)((M + 63) / 64), 2 * uy, 1);
-    } else if (few_small) {
-        r->kernel = few_bm == 64 ? ConvKernel::ws_64_4_4_3 : ConvKernel::ws_128_4_8_5;
-        r->grid = dim3((unsigned)((M + few_bm - 1) / few_bm), uy, S);
-    } else if (kw_ks) {
-        r->kernel = kw_ks == 4 ? ConvKernel::kw_4_1 : kw_ks == 2 ? ConvKernel::kw_2_2 : ConvKernel::none;
-        snprintf(r->unbuilt, sizeof(r->unbuilt), "conv_kw_ks=%d (2 or 4)", kw_ks);
-        r->grid = dim3((unsigned)((M + 63) / 64), kw_ks == 4 ? 2 * uy : uy, S);
-    } else if (st_bm) {
-        const int np = vo("conv_st_np"), ns = vo("conv_st_ns");
-        if (st_bm == 64 && np == 4 && ns == 3) r->kernel = ConvKernel::ws_64_4_4_3;
-        else if (st_bm == 64 && np == 4 && ns == 6) r->kernel = ConvKernel::ws_64_4_4_6;
-        else if (st_bm == 128 && np == 4 && ns == 3) r->kernel = ConvKernel::ws_128_4_4_3;
-        else if (st_bm == 128 && np == 8 && ns == 3) r->kernel = ConvKernel::ws_128_4_8_3;
-        else if (st_bm == 128 && np == 8 && ns == 5) r->kernel = ConvKernel::ws_128_4_8_5;
-        else snprintf(r->unbuilt, sizeof(r->unbuilt), "conv_st_bm=%d conv_st_np=%d conv_st_ns=%d is not a built tile", st_bm, np, ns);
-        r->grid = dim3((unsigned)((M + st_bm - 1) / st_bm), uy, S);
-    } else if (deep) {
-        S = 1;
-        r->kernel = ConvKernel::linear_deep;
-        r->grid = dim3((unsigned)((M + 63) / 64), uy, 1);
-    } else if (route256) {
-        r->grid = dim3((unsigned)((M + 255) / 256), uy, S);
-        if (ncb > 1) {
-            r->kernel = ConvKernel::linear_ws;
-            r->grid = dim3(r->grid.x, (unsigned)(ntn / ncb), 1);
-        } else if (ws && (!geglu || !upm)) {
-            // 3x3x3 SAME convs on volumes with W <= 16: the A tile of a (chunk, kd, kh) group staged once, the kw = -1 / +1 operands
-            // shifted in registers (k_conv_ws3; bit-identical to k_conv_ws).  ES_CONV_A3 = 0 / 1: timing-only A/B switch
-            static const char* a3_env = getenv("ES_CONV_A3");
-            const bool a3 = (a3_env ? atoi(a3_env) != 0 : ES_CONV_A3_DEFAULT) && a->taps == 27 && a->mode == ES_CONV_SAME && !a->a2 && a->W <= 16 && a->W >= 4;
-            r->kernel = a3 ? ConvKernel::ws3 : ConvKernel::ws_256_8_4_3;
-            // An UP_HW launch that carries its folded image (w2, read by no other UP launch: they have no skip phase) multiplies 12 folded
-            // taps per chunk instead of 27 (k_conv_ws_fold) -- only here: an unsplit launch of a non-sharded plan (O_hint == 0: the
-            // canonical and the sharded arithmetic stay the 27-tap one) whose 256-row tiles are each one parity class of one object.
-            // Other products than the 27-tap route's (the folded weights are rounded after the sum): not bit-equal to it.
-            if (r->kernel == ConvKernel::ws_256_8_4_3 && a->mode == ES_CONV_UP_HW && a->w2 && !a->a2 && S == 1 && a->O_hint == 0 &&
-                a->H >= 2 && a->W >= 2 && ((long)a->D * g.Hi * g.Wi) % 256 == 0) {
-                r->kernel = ConvKernel::ws_256_up_fold;
-                // three column tiles, no workspace, on a grid whose last round of 256 workgroups is mostly empty (384 tiles: 75 % of two rounds):
-                // 2 workgroups per row tile, each one whole tile and half of the third column tile (k_conv_ws_fold_bal) -- the same
-                // sums in the same order, S stays 1
-                const long rounds = (wg256 + 255) / 256;
-                if (ntn == 3 && !a->workspace && M % 256 == 0 && (double)wg256 / (double)(rounds * 256) < 0.8) {
-                    r->fold_bal = true;
-                    r->grid = dim3(r->grid.x, 2, 1);
-                }
-            }
-        } else
-            r->kernel = ConvKernel::lean_256;
-    } else if ((wg128 >= 512 || S > 1) && !tiny_split) {
-        r->kernel = ConvKernel::lean_128;
-        r->grid = dim3((unsigned)((M + 127) / 128), uy, S);
-    } else {
-        r->kernel = ConvKernel::lean_64;
-        r->grid = dim3((unsigned)((M + 63) / 64), uy, tiny_split ? S : 1);
-    }
-    r->S = S;
-    if (S > 1) {
-        r->reduce = a->gn_part_out && part_ok ? ConvReduce::gn_part : ConvReduce::plain;
-        if (r->reduce == ConvReduce::gn_part) r->vt = gn_voxel_tile(Oh, a->D * a->H * a->W);
-    }
-    return 0;
-}
 
 // k_conv_ws launcher for one (tile rows, consumer waves, producer waves, ring depth): the 256-row tile of rounds 1-5 (8 consumers as
 // 4 x 2, 4 producers) and, round 6, the few-objects tiles of 64 / 128 rows (4 consumers as 2 x 2 of BM_/2 x 112, 4 or 8 producers,
@@ -3377,18 +2964,18 @@ static int launch_ws(const es_conv_args* a, const ConvRoute& r, hipStream_t st) 
                                {(const void*)k_conv_ws<BM_, NC_, NP_, false, ES_EPI_GEGLU, false, NS_>, LDS}};
     ES_REQUIRE(lim.err == hipSuccess, "es_conv_mfma_f16: hipFuncSetAttribute failed: %s", hipGetErrorString(lim.err));
     const dim3 blk(64 * (NC_ + NP_));
-    if (r.geglu) hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, false, ES_EPI_GEGLU, false, NS_>), r.grid, blk, LDS, st, *a, r.g, r.ncdhw);
+    if (r.geglu) hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, false, ES_EPI_GEGLU, false, NS_>), grid_of(r), blk, LDS, st, *a, r.g, r.ncdhw);
     else if (r.stats) {
         if constexpr (CAN_STATS) {
             static const LdsLimits lim_stats{{(const void*)k_conv_ws<BM_, NC_, NP_, false, ES_EPI_NONE, true, NS_>, LDS},
                                              {(const void*)k_conv_ws<BM_, NC_, NP_, true, ES_EPI_NONE, true, NS_>, LDS}};
             ES_REQUIRE(lim_stats.err == hipSuccess, "es_conv_mfma_f16: hipFuncSetAttribute failed: %s", hipGetErrorString(lim_stats.err));
-            if (r.upm) hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, true, ES_EPI_NONE, true, NS_>), r.grid, blk, LDS, st, *a, r.g, r.ncdhw);
-            else hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, false, ES_EPI_NONE, true, NS_>), r.grid, blk, LDS, st, *a, r.g, r.ncdhw);
+            if (r.upm) hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, true, ES_EPI_NONE, true, NS_>), grid_of(r), blk, LDS, st, *a, r.g, r.ncdhw);
+            else hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, false, ES_EPI_NONE, true, NS_>), grid_of(r), blk, LDS, st, *a, r.g, r.ncdhw);
         } else ES_REQUIRE(false, "launch_ws: row-group sums need 64-row waves");
     }
-    else if (r.upm) hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, true, ES_EPI_NONE, false, NS_>), r.grid, blk, LDS, st, *a, r.g, r.ncdhw);
-    else hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, false, ES_EPI_NONE, false, NS_>), r.grid, blk, LDS, st, *a, r.g, r.ncdhw);
+    else if (r.upm) hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, true, ES_EPI_NONE, false, NS_>), grid_of(r), blk, LDS, st, *a, r.g, r.ncdhw);
+    else hipLaunchKernelGGL((k_conv_ws<BM_, NC_, NP_, false, ES_EPI_NONE, false, NS_>), grid_of(r), blk, LDS, st, *a, r.g, r.ncdhw);
     return 0;
 }
 
@@ -3402,9 +2989,9 @@ static int launch_kw(const es_conv_args* a, const ConvRoute& r, hipStream_t st) 
                                {(const void*)k_conv_kw<KS_, NCH_, false, ES_EPI_GEGLU>, LDS}};
     ES_REQUIRE(lim.err == hipSuccess, "es_conv_mfma_f16: hipFuncSetAttribute failed: %s", hipGetErrorString(lim.err));
     const dim3 blk(768);
-    if (r.geglu) hipLaunchKernelGGL((k_conv_kw<KS_, NCH_, false, ES_EPI_GEGLU>), r.grid, blk, LDS, st, *a, r.g, r.ncdhw);
-    else if (r.upm) hipLaunchKernelGGL((k_conv_kw<KS_, NCH_, true, ES_EPI_NONE>), r.grid, blk, LDS, st, *a, r.g, r.ncdhw);
-    else hipLaunchKernelGGL((k_conv_kw<KS_, NCH_, false, ES_EPI_NONE>), r.grid, blk, LDS, st, *a, r.g, r.ncdhw);
+    if (r.geglu) hipLaunchKernelGGL((k_conv_kw<KS_, NCH_, false, ES_EPI_GEGLU>), grid_of(r), blk, LDS, st, *a, r.g, r.ncdhw);
+    else if (r.upm) hipLaunchKernelGGL((k_conv_kw<KS_, NCH_, true, ES_EPI_NONE>), grid_of(r), blk, LDS, st, *a, r.g, r.ncdhw);
+    else hipLaunchKernelGGL((k_conv_kw<KS_, NCH_, false, ES_EPI_NONE>), grid_of(r), blk, LDS, st, *a, r.g, r.ncdhw);
     return 0;
 }
 
@@ -3412,8 +2999,8 @@ static int launch_kw(const es_conv_args* a, const ConvRoute& r, hipStream_t st) 
 template <int BM_, int NW_>
 static void launch_lean(const es_conv_args* a, const ConvRoute& r, hipStream_t st) {
     constexpr int LDS = 3 * (BM_ * BK * 2 + BNP * BK * 2);
-    if (r.upm) hipLaunchKernelGGL((k_conv_lean<BM_, NW_, true>), r.grid, dim3(64 * NW_), LDS, st, *a, r.g, r.ncdhw);
-    else hipLaunchKernelGGL((k_conv_lean<BM_, NW_>), r.grid, dim3(64 * NW_), LDS, st, *a, r.g, r.ncdhw);
+    if (r.upm) hipLaunchKernelGGL((k_conv_lean<BM_, NW_, true>), grid_of(r), dim3(64 * NW_), LDS, st, *a, r.g, r.ncdhw);
+    else hipLaunchKernelGGL((k_conv_lean<BM_, NW_>), grid_of(r), dim3(64 * NW_), LDS, st, *a, r.g, r.ncdhw);
 }
 
 // Row-group sums of gn_stats_out by a pass over the finished fp32 output of `rows` rows
@@ -3445,10 +3032,10 @@ static int conv_launch(const es_conv_args* a, const ConvRoute& r, hipStream_t st
     case ConvKernel::small_n_tiled:
         ES_REQUIRE(a->mode == ES_CONV_SAME && !a->a2 && !a->res && !a->rowvec && !a->out_f16 && !a->gn_stats_out,
                    "es_conv_mfma_f16: the N<=4, Cin<=64 direct kernel takes SAME mode, fp32 output, no fusions");
-        if (r.kernel == ConvKernel::small_n_tiled) hipLaunchKernelGGL(k_conv_small_n_tiled, r.grid, dim3(256), r.lds, st, *a, r.g, r.ncdhw);
-        else hipLaunchKernelGGL(k_conv_small_n, r.grid, dim3(256), r.lds, st, *a, r.g, r.ncdhw);
+        if (r.kernel == ConvKernel::small_n_tiled) hipLaunchKernelGGL(k_conv_small_n_tiled, grid_of(r), dim3(256), r.lds, st, *a, r.g, r.ncdhw);
+        else hipLaunchKernelGGL(k_conv_small_n, grid_of(r), dim3(256), r.lds, st, *a, r.g, r.ncdhw);
         break;
-    case ConvKernel::n16: hipLaunchKernelGGL(k_conv_n16, r.grid, dim3(256), N16_A_BYTES + N16_B_BYTES, st, *a, r.g); break;
+    case ConvKernel::n16: hipLaunchKernelGGL(k_conv_n16, grid_of(r), dim3(256), N16_A_BYTES + N16_B_BYTES, st, *a, r.g); break;
     case ConvKernel::kw_4_1: rc = launch_kw<4, 1>(a, r, st); break;
     case ConvKernel::kw_2_2: rc = launch_kw<2, 2>(a, r, st); break;
     case ConvKernel::ws_256_8_4_3: rc = launch_ws<256, 8, 4, 3>(a, r, st); break;
@@ -3458,21 +3045,21 @@ static int conv_launch(const es_conv_args* a, const ConvRoute& r, hipStream_t st
     case ConvKernel::ws_128_4_8_3: rc = launch_ws<128, 4, 8, 3>(a, r, st); break;
     case ConvKernel::ws_128_4_8_5: rc = launch_ws<128, 4, 8, 5>(a, r, st); break;
     case ConvKernel::ws3:
-        if (r.stats) hipLaunchKernelGGL((k_conv_ws3<true>), r.grid, dim3(768), LDSWS3, st, *a, r.g);
-        else hipLaunchKernelGGL((k_conv_ws3<false>), r.grid, dim3(768), LDSWS3, st, *a, r.g);
+        if (r.stats) hipLaunchKernelGGL((k_conv_ws3<true>), grid_of(r), dim3(768), LDSWS3, st, *a, r.g);
+        else hipLaunchKernelGGL((k_conv_ws3<false>), grid_of(r), dim3(768), LDSWS3, st, *a, r.g);
         break;
     case ConvKernel::ws_256_up_fold:
         if (r.fold_bal) {
-            if (r.stats) hipLaunchKernelGGL((k_conv_ws_fold_bal<true>), r.grid, dim3(768), LDS256, st, *a, r.g);
-            else hipLaunchKernelGGL((k_conv_ws_fold_bal<false>), r.grid, dim3(768), LDS256, st, *a, r.g);
-        } else if (r.stats) hipLaunchKernelGGL((k_conv_ws_fold<true>), r.grid, dim3(768), LDS256, st, *a, r.g);
-        else hipLaunchKernelGGL((k_conv_ws_fold<false>), r.grid, dim3(768), LDS256, st, *a, r.g);
+            if (r.stats) hipLaunchKernelGGL((k_conv_ws_fold_bal<true>), grid_of(r), dim3(768), LDS256, st, *a, r.g);
+            else hipLaunchKernelGGL((k_conv_ws_fold_bal<false>), grid_of(r), dim3(768), LDS256, st, *a, r.g);
+        } else if (r.stats) hipLaunchKernelGGL((k_conv_ws_fold<true>), grid_of(r), dim3(768), LDS256, st, *a, r.g);
+        else hipLaunchKernelGGL((k_conv_ws_fold<false>), grid_of(r), dim3(768), LDS256, st, *a, r.g);
         break;
     case ConvKernel::linear_ws:
-        if (r.geglu) hipLaunchKernelGGL((k_linear_ws<ES_EPI_GEGLU>), r.grid, dim3(768), LDSLIN, st, *a, r.g, r.ncb);
-        else hipLaunchKernelGGL((k_linear_ws<ES_EPI_NONE>), r.grid, dim3(768), LDSLIN, st, *a, r.g, r.ncb);
+        if (r.geglu) hipLaunchKernelGGL((k_linear_ws<ES_EPI_GEGLU>), grid_of(r), dim3(768), LDSLIN, st, *a, r.g, r.ncb);
+        else hipLaunchKernelGGL((k_linear_ws<ES_EPI_NONE>), grid_of(r), dim3(768), LDSLIN, st, *a, r.g, r.ncb);
         break;
-    case ConvKernel::linear_deep: hipLaunchKernelGGL(k_linear_deep, r.grid, dim3(256), LDSDEEP, st, *a, r.g); break;
+    case ConvKernel::linear_deep: hipLaunchKernelGGL(k_linear_deep, grid_of(r), dim3(256), LDSDEEP, st, *a, r.g); break;
     case ConvKernel::lean_256: launch_lean<256, 8>(a, r, st); break;
     case ConvKernel::lean_128: launch_lean<128, 4>(a, r, st); break;
     case ConvKernel::lean_64: launch_lean<64, 4>(a, r, st); break;
@@ -3497,79 +3084,24 @@ static int conv_launch(const es_conv_args* a, const ConvRoute& r, hipStream_t st
 
 extern "C" int es_conv_mfma_f16(const es_conv_args* a, es_stream stream) {
     ConvRoute r;
-    if (int rc = conv_route(a, &r)) return rc;
+    if (int rc = conv_route(*a, es_route_options(), &r)) return rc;
     const hipStream_t st = (hipStream_t)stream;
     if (!r.omax) return conv_launch(a, r, st);
     // over the descriptor limit: chunks of r.omax objects, each routed and launched for itself (the last one may be smaller and pick
     // its own tile; O_hint keeps the split-K choice of the whole problem), then one statistics pass over the whole tensor
-    const long V = (long)a->D * a->H * a->W;
-    const long per_obj_in = (long)r.g.Di * r.g.Hi * r.g.Wi * a->Cin * 2, per_obj_in2 = a->a2 ? V * a->Cin2 * 2 : 0;
     for (long o0 = 0; o0 < a->O; o0 += r.omax) {
-        es_conv_args c = *a;
-        c.O = (int32_t)std::min(r.omax, (long)a->O - o0);
-        c.O_hint = a->O_hint < 0 ? a->O_hint : (a->O_hint > a->O ? a->O_hint : a->O);
-        c.a = (const char*)a->a + o0 * per_obj_in;
-        if (a->a2) c.a2 = (const char*)a->a2 + o0 * per_obj_in2;
-        if (a->rowvec) c.rowvec = a->rowvec + o0 * a->rowvec_ld;
-        if (r.ncdhw) {
-            c.out_f32 = a->out_f32 + o0 * a->N * V;
-        } else {
-            if (a->res) c.res = a->res + o0 * V * a->out_ld;
-            if (a->out_f32) c.out_f32 = a->out_f32 + o0 * V * a->out_ld;
-            if (a->out_f16) c.out_f16 = (char*)a->out_f16 + o0 * V * a->out_ld * 2;
-        }
-        c.gn_stats_out = c.gn_part_out = nullptr;  // (the planes are laid out for the whole tensor: one pass below; partials: never asked for)
+        const es_conv_args c = conv_chunk_args(*a, r.g, o0, std::min(r.omax, (long)a->O - o0));
         ConvRoute rc;
-        if (int err = conv_route(&c, &rc)) return err;
+        if (int err = conv_route(c, es_route_options(), &rc)) return err;
         if (int err = conv_launch(&c, rc, st)) return err;
     }
     if (r.stats_pass) {
-        ES_REQUIRE(a->out_f32 && !r.ncdhw && a->N % 4 == 0 && a->out_ld % 4 == 0 && V % 64 == 0, "es_conv_mfma_f16: gn_stats_out needs a channels-last fp32 output");
+        ES_REQUIRE(a->out_f32 && !r.ncdhw && a->N % 4 == 0 && a->out_ld % 4 == 0 && ((long)a->D * a->H * a->W) % 64 == 0,
+                   "es_conv_mfma_f16: gn_stats_out needs a channels-last fp32 output");
         launch_rowgroup_stats(a, r.M, st);
         ES_CHECK_HIP(hipGetLastError());
     }
     return 0;
-}
-
-// 1 when es_conv_mfma_f16(args) would form gn_stats_out inside its own epilogue (the planner only asks a conv for the sums then:
-// behind any other route they would cost a pass over the output, i.e. what the GroupNorm's own statistics pass costs), 0 when
-// not, -1 on invalid arguments.  Host-only: launches nothing.
-extern "C" int es_conv_emits_gn_stats(const es_conv_args* a) {
-    ConvRoute r;
-    return conv_route(a, &r) == 0 ? (int)r.epi_stats : -1;
-}
-
-// 1 when a split launch's reduction kernel can form the next GroupNorm's per-tile partial sums (gn_part_out), 0 when not, -1 on
-// invalid arguments.  Host-only.
-extern "C" int es_conv_emits_gn_part(const es_conv_args* a) {
-    ConvRoute r;
-    return conv_route(a, &r) == 0 ? (int)r.part_ok : -1;
-}
-
-// The number of fp32 slabs [S][M][N] es_conv_mfma_f16(args) writes into args->workspace (1: none -- no split, or K split inside the
-// workgroup), -1 on invalid arguments.  Host-only: the planner sizes the workspace with it.
-extern "C" int es_conv_split_of(const es_conv_args* a) {
-    ConvRoute r;
-    return conv_route(a, &r) == 0 ? r.slabs : -1;
-}
-
-// The name of the kernel es_conv_mfma_f16(args) would launch (the ConvKernel enumerator's spelling; "chunked" for a launch over the
-// 2 GiB descriptor limit, whose chunks are routed one by one; "none" for forcing options that name a tile that is not built),
-// written into name_out (cap bytes, always terminated); returns the split of K over workgroups (ConvRoute::S, >= 1; a chunked
-// launch: of a full chunk), -1 on invalid arguments.  Host-only: tests assert with it that the kernel they mean is the one that ran.
-extern "C" int es_conv_kernel_of(const es_conv_args* a, char* name_out, int cap) {
-    ConvRoute r;
-    if (conv_route(a, &r) != 0) return -1;
-    if (name_out && cap > 0) snprintf(name_out, (size_t)cap, "%s", r.omax ? "chunked" : kConvKernelName[(int)r.kernel]);
-    return r.S > 1 ? r.S : 1;
-}
-
-// 1 when es_conv_mfma_f16(args) takes the folded route on its balanced schedule (ConvRoute::fold_bal: three column tiles on a grid
-// whose last round is mostly empty -- two workgroups per row tile, each one tile and a half), 0 when not, -1 on invalid arguments.
-// Host-only; the kernel name and the split that es_conv_kernel_of reports do not depend on it.
-extern "C" int es_conv_fold_balanced(const es_conv_args* a) {
-    ConvRoute r;
-    return conv_route(a, &r) == 0 ? (int)r.fold_bal : -1;
 }
 
 extern "C" int es_groupnorm_vol(const es_gn_args* a, es_stream stream) {
@@ -3583,7 +3115,7 @@ extern "C" int es_groupnorm_vol(const es_gn_args* a, es_stream stream) {
     const int vt = gn_voxel_tile(Oh, a->V);
     const int ntiles = (a->V + vt - 1) / vt;
     float* part = a->stats;      // caller-provided scratch of O*ceil(V/8)*groups*2 floats
-    const bool from_rg = a->stats1 && (!a->x2 || a->stats2) && a->V % 64 == 0 && (a->x1_is_f16 || vo("gn_rg") != 0);
+    const bool from_rg = a->stats1 && (!a->x2 || a->stats2) && a->V % 64 == 0 && (a->x1_is_f16 || es_route_options().gn_rg != 0);
     ES_REQUIRE(!a->x1_is_f16 || (from_rg && !a->x2 && !a->raw_f16),
                "es_groupnorm_vol: an f16 source needs the producer's row-group sums (stats1), one source, no raw copy");
     ES_REQUIRE(!a->part_in || (!from_rg && !a->x2), "es_groupnorm_vol: part_in needs one source and no row-group sums");

@@ -64,6 +64,18 @@ class ConvArgs(C.Structure):
                 ('epilogue', C.c_int32), ('gn_stats_out', C.c_void_p), ('gn_part_out', C.c_void_p), ('gn_part_groups', C.c_int32)]
 
 
+class ConvRouteInfo(C.Structure):
+    """es_conv_route_info: every field of a conv launch's route (es_conv_route_of; host-only, for tests and tools)"""
+    _fields_ = [('kernel', C.c_int32), ('grid_x', C.c_uint32), ('grid_y', C.c_uint32), ('grid_z', C.c_uint32)] + \
+               [(f, C.c_int32) for f in ('lds', 'S', 'slabs', 'ncb', 'omax', 'epi_stats', 'stats', 'stats_pass', 'part_ok', 'reduce', 'vt',
+                                         'fold_bal')]
+
+
+# the library's kernel names in the order of es_conv_route_info.kernel (csrc/es_conv_route.h: kConvKernelName)
+CONV_KERNELS = ('none', 'small_n', 'small_n_tiled', 'n16', 'kw_4_1', 'kw_2_2', 'ws_256_8_4_3', 'ws_64_4_4_3', 'ws_64_4_4_6', 'ws_128_4_4_3',
+                'ws_128_4_8_3', 'ws_128_4_8_5', 'ws3', 'ws_256_up_fold', 'linear_ws', 'linear_deep', 'lean_256', 'lean_128', 'lean_64')
+
+
 class GNArgs(C.Structure):
     _fields_ = [('x1', C.c_void_p), ('C1', C.c_int32), ('x2', C.c_void_p), ('C2', C.c_int32), ('O', C.c_int32),
                 ('V', C.c_int32), ('groups', C.c_int32), ('eps', C.c_float), ('gamma', C.c_void_p),
@@ -209,6 +221,7 @@ EXPORTS = {
     'es_conv_split_of': (C.c_int, [C.POINTER(ConvArgs)]),
     'es_conv_kernel_of': (C.c_int, [C.POINTER(ConvArgs), C.c_char_p, C.c_int]),
     'es_conv_fold_balanced': (C.c_int, [C.POINTER(ConvArgs)]),
+    'es_conv_route_of': (C.c_int, [C.POINTER(ConvArgs), C.POINTER(ConvRouteInfo)]),
     'es_split_f16x3': (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p]),
     'es_pack_conv_f16_size': (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     'es_pack_conv_f16': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),

@@ -452,6 +452,28 @@ int es_conv_kernel_of(const es_conv_args* args, char* name_out, int cap);
  * and half of the third column tile.  The same sums in the same order as the plain schedule; the name and the split reported by
  * es_conv_kernel_of do not change.  0 when not, -1 on invalid arguments.  For tests and tools.  Launches nothing. */
 int es_conv_fold_balanced(const es_conv_args* args);
+/* host-only: every field of the route es_conv_mfma_f16(args) would take, under the process's route options.  The five queries above
+ * read one field each of the same answer.  For tests and tools (tests/golden/conv_routes.npz pins all of them); the kernel index and
+ * the grid are no part of the numerics contract.  Returns 0, or -1 on invalid arguments (es_last_error(); *out is then untouched).
+ * Launches nothing. */
+typedef struct es_conv_route_info {
+    int32_t kernel;                     /* index of the kernel's name in the library's list, as es_conv_kernel_of spells it (0: "none" --
+                                           a chunked launch, or forcing options that name a tile that is not built) */
+    uint32_t grid_x, grid_y, grid_z;    /* workgroups of the launch (a chunked launch: 1, 1, 1) */
+    int32_t lds;                        /* dynamic LDS bytes where the route decides them (the direct N <= 4 kernels), else 0 */
+    int32_t S;                          /* split of K over workgroups (1: none; a chunked launch: of a full chunk) */
+    int32_t slabs;                      /* es_conv_split_of */
+    int32_t ncb;                        /* linear_ws: column tiles one workgroup walks (else 1; 0 for the direct kernels and chunked launches) */
+    int32_t omax;                       /* > 0: over the 2 GiB descriptor limit, launched in chunks of omax objects */
+    int32_t epi_stats;                  /* es_conv_emits_gn_stats */
+    int32_t stats;                      /* ... and gn_stats_out is given: the epilogue forms the sums in this launch */
+    int32_t stats_pass;                 /* gn_stats_out is formed by a pass over the finished output */
+    int32_t part_ok;                    /* es_conv_emits_gn_part */
+    int32_t reduce;                     /* 0: no reduction launch, 1: the plain split-K reduction, 2: the one that writes gn_part_out */
+    int32_t vt;                         /* reduce == 2: voxel tile of the partial sums (else 0) */
+    int32_t fold_bal;                   /* es_conv_fold_balanced */
+} es_conv_route_info;
+int es_conv_route_of(const es_conv_args* args, es_conv_route_info* out);
 /* Split-operand image of an fp32 activation [M, C] (C % 4 == 0): out f16 [M, 3 C] = [hi | lo | hi], hi = f16(x), lo = f16(x - hi).
  * Against a weight image packed from [w_hi | w_hi | w_lo] (Cin = 3 C) es_conv_mfma_f16 accumulates hi w_hi + lo w_hi + hi w_lo in
  * fp32: the reference's fp32 arithmetic to ~2^-21 per product on the f16 matrix pipe (ShapeDenoiser(precision='fp32x')). */

@@ -19,7 +19,7 @@ SAME, DOWN_HW, UP_HW, UP_DHW, DOWN_DHW, DOWN_DHW_P01 = range(6)
 MODE_NAMES = {SAME: 'same', DOWN_HW: 'down_hw', UP_HW: 'up_hw', UP_DHW: 'up_dhw', DOWN_DHW: 'down_dhw', DOWN_DHW_P01: 'down_dhw_p01'}
 UP_MODES = (UP_HW, UP_DHW)
 
-# every value of the library's ConvKernel enum (es_vol.hip), 'none' excluded
+# every value of the library's ConvKernel enum (csrc/es_conv_route.h), 'none' excluded
 KERNELS = ('small_n', 'small_n_tiled', 'n16', 'kw_4_1', 'kw_2_2', 'ws_256_8_4_3', 'ws_64_4_4_3', 'ws_64_4_4_6', 'ws_128_4_4_3',
            'ws_128_4_8_3', 'ws_128_4_8_5', 'ws3', 'linear_ws', 'linear_deep', 'lean_256', 'lean_128', 'lean_64')
 # the kernels whose operand addressing handles the conv modes (k_conv_lean, k_conv_ws, k_conv_kw): each must be reached in all six

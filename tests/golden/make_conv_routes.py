@@ -1,12 +1,14 @@
-"""Writes conv_routes.npz: the answers of the three host-only routing queries of es_conv_mfma_f16 (es_conv_emits_gn_stats,
-es_conv_emits_gn_part, es_conv_split_of) over a grid of es_conv_args crossed with route-option settings.  No device is needed: the
-queries launch nothing.  tests/test_conv_route_cpu.py replays the table against the built library, so a change of the routing rule
+"""Writes conv_routes.npz: every field of the route of es_conv_mfma_f16 (es_conv_route_of: kernel, grid, LDS bytes, split, slabs,
+column tiles per workgroup, chunk size, the statistics and reduction flags, the folded route's schedule) over a grid of es_conv_args
+crossed with route-option settings.  No device is needed: the query launches nothing.  tests/test_conv_route_cpu.py replays the table against the built library, so a change of the routing rule
 shows as a changed entry; regenerate the file only when such a change is intended, and say so in the commit.
 
-usage: python tests/golden/make_conv_routes.py          (against the library built in this tree)
+usage: python tests/golden/make_conv_routes.py               (against the library built in this tree)
+       python tests/golden/make_conv_routes.py --check-old   (writes nothing: are the committed file's values, for its cases, still the answers?)
 
 The file holds the case table (one row of small integers per es_conv_args, columns = COLS), the option settings, the option
-values they start from and the answers [setting][case][query] -- no pointers, no tensors."""
+values they start from and one array [setting][case] per route field (FIELDS, each in the narrowest integer type that holds it; -1 in
+every field where the arguments are refused) -- no pointers, no tensors."""
 import ctypes as C
 import itertools
 import os
@@ -20,7 +22,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 # one case = one row of these; the flag columns say which optional pointers are non-NULL (the queries never dereference them)
 COLS = ('O', 'D', 'H', 'W', 'Cin', 'N', 'taps', 'mode', 'Cin2', 'epilogue', 'splitk', 'workspace', 'O_hint',
         'out',                 # 0: fp32 channels-last, 1: fp16 channels-last, 2: fp32 NCDHW (out_ld < 0), 3: no output at all
-        'gn_stats_out', 'gn_part_out', 'gn_part_groups', 'rowvec', 'res')
+        'gn_stats_out', 'gn_part_out', 'gn_part_groups', 'rowvec', 'res',
+        'w2')                  # 1: w2 WITHOUT a2 -- the folded weight image of an UP_HW launch
+
+# the fields of es_conv_route_info, in its order
+FIELDS = ('kernel', 'grid_x', 'grid_y', 'grid_z', 'lds', 'S', 'slabs', 'ncb', 'omax', 'epi_stats', 'stats', 'stats_pass', 'part_ok', 'reduce',
+          'vt', 'fold_bal')
 
 # route-option settings: '' = the defaults, otherwise name=value pairs set on top of the defaults
 SETTINGS = ('', 'conv_few=0', 'conv_wssplit=0', 'conv_wss_target=512', 'conv_tile=128', 'conv_force256=1', 'conv_ws=0', 'conv_deep=0',
@@ -43,11 +50,11 @@ UNET_VOLS = ((16, 16, 16), (16, 8, 8), (16, 4, 4))
 VQVAE_VOLS = ((16, 16, 16), (32, 32, 32), (64, 64, 64))            # 32 objects at 64^3 with Cin = 128: over 2 GiB, the chunked branch
 
 
-def case(O, vol, layer, splitk=-1, workspace=1, hint=0, mode=0, out=0, gn_stats=0, gn_part=0, groups=0, rowvec=0, res=0):
+def case(O, vol, layer, splitk=-1, workspace=1, hint=0, mode=0, out=0, gn_stats=0, gn_part=0, groups=0, rowvec=0, res=0, w2=0):
     cin, n, taps, cin2, epi = layer
     if epi and out == 0:
         out = 1                                                    # the GEGLU epilogue writes fp16 only
-    return (O, vol[0], vol[1], vol[2], cin, n, taps, mode, cin2, epi, splitk, workspace, hint, out, gn_stats, gn_part, groups, rowvec, res)
+    return (O, vol[0], vol[1], vol[2], cin, n, taps, mode, cin2, epi, splitk, workspace, hint, out, gn_stats, gn_part, groups, rowvec, res, w2)
 
 
 def cases():
@@ -88,6 +95,14 @@ def cases():
     rows.append(case(4, (16, 16, 16), ok, out=2, res=1))           # NCDHW with a residual
     rows.append(case(4, (16, 16, 16), (224, 3, 27, 0, 0), gn_stats=1))
     rows.append(case(4, (16, 4, 2), ok, gn_stats=1))               # 32 voxels per object
+    # UP_HW launches that carry their folded image (w2 without a2): the two up-sampling convs of the shape UNet (448 -> 448 at 16^3,
+    # 672 -> 672 at 16x8x8, whose 384 tiles take the balanced schedule), 224 -> 224 at 16^3, and a volume whose D * H/2 * W/2 is no
+    # multiple of 256 (16x4x4) -- with and without a workspace, whole problems, canonical shards and hinted shards.  Appended behind
+    # the older cases, so that their indices stay what they were
+    for O, hint, workspace, splitk in itertools.product(OBJECTS + (64,), HINTS, (0, 1), (-1, 0)):
+        for vol, layer in (((16, 16, 16), UNET[2]), ((16, 8, 8), UNET[4]), ((16, 16, 16), UNET[0]), ((16, 4, 4), UNET[4])):
+            rows.append(case(O, vol, layer, splitk, workspace, hint, mode=2, w2=1))
+            rows.append(case(O, vol, layer, splitk, workspace, hint, mode=2, w2=1, gn_stats=1))
     return np.asarray(rows, dtype=np.int32)
 
 
@@ -99,6 +114,8 @@ def conv_args(hip, row):
         setattr(a, k, r[k])
     if r['Cin2']:
         a.a2, a.w2, a.Cin2 = 0x1100, 0x2100, r['Cin2']
+    if r['w2']:
+        a.w2 = 0x2100
     a.out_ld = -1 if r['out'] == 2 else (r['N'] // 2 if r['epilogue'] else r['N'])
     a.out_f32 = 0x3000 if r['out'] in (0, 2) else None
     a.out_f16 = 0x4000 if r['out'] == 1 else None
@@ -118,32 +135,52 @@ def route_options(hip):
 
 
 def answers(hip, table, settings):
-    """[setting][case][emits_gn_stats, emits_gn_part, split_of]; every option a setting changes is restored"""
+    """[setting][case][field of FIELDS], -1 in every field where the arguments are refused; every option a setting changes is restored"""
     L = hip.lib()
     defaults = dict(kv.split('=') for kv in route_options(hip).strip(';').split(';'))
     structs = [conv_args(hip, row) for row in table]
-    out = np.zeros((len(settings), len(structs), 3), dtype=np.int8)
+    out = np.full((len(settings), len(structs), len(FIELDS)), -1, dtype=np.int64)
+    info = hip.ConvRouteInfo()
     for si, setting in enumerate(settings):
         pairs = [kv.split('=') for kv in str(setting).split(',') if kv]
         try:
             for k, v in pairs:
                 hip.check(L.es_vol_set_option(k.encode(), int(v)), 'es_vol_set_option')
             for ci, a in enumerate(structs):
-                p = C.byref(a)
-                out[si, ci] = (L.es_conv_emits_gn_stats(p), L.es_conv_emits_gn_part(p), L.es_conv_split_of(p))
+                if L.es_conv_route_of(C.byref(a), C.byref(info)) == 0:
+                    out[si, ci] = [getattr(info, f) for f in FIELDS]
         finally:
             for k, _ in pairs:
                 hip.check(L.es_vol_set_option(k.encode(), int(defaults[k])), 'es_vol_set_option')
     return out
 
 
+def narrow(v):
+    """v in the smallest signed integer type that holds all of it"""
+    for t in (np.int8, np.int16, np.int32):
+        if np.iinfo(t).min <= v.min() and v.max() <= np.iinfo(t).max:
+            return v.astype(t)
+    raise ValueError('a route field beyond 32 bits')
+
+
 if __name__ == '__main__':
     from echoscene_amd import hip
     table = cases()
     ans = answers(hip, table, SETTINGS)
-    np.savez_compressed(os.path.join(HERE, 'conv_routes.npz'), cols=np.asarray(COLS), cases=table, settings=np.asarray(SETTINGS), answers=ans,
-                        defaults=np.asarray(route_options(hip)))          # the option values every setting starts from
-    triples, counts = np.unique(ans.reshape(-1, 3), axis=0, return_counts=True)
-    print('%d cases x %d settings, %d distinct answers:' % (len(table), len(SETTINGS), len(triples)))
-    for t, c in zip(triples, counts):
-        print('  stats %2d part %2d slabs %2d : %d' % (t[0], t[1], t[2], c))
+    path = os.path.join(HERE, 'conv_routes.npz')
+    if '--check-old' in sys.argv:
+        # before a regeneration that only ADDS cases or fields: what the committed file holds, for the cases it holds, must be what
+        # the library gives now (exit status 1 if not; nothing is written)
+        old = np.load(path)
+        n, w = old['cases'].shape
+        assert (old['cases'] == table[:n, :w]).all() and not table[:n, w:].any() and [str(s) for s in old['settings']] == list(SETTINGS)
+        moved = sum(int((ans[:, :n, FIELDS.index(str(f))] != old['f_' + str(f)]).sum()) for f in old['fields'])
+        print('%d old cases x %d settings x %d fields: %d recorded values differ' % (n, len(SETTINGS), len(old['fields']), moved))
+        sys.exit(int(moved != 0))
+    np.savez_compressed(path, cols=np.asarray(COLS), cases=table, settings=np.asarray(SETTINGS), fields=np.asarray(FIELDS),
+                        defaults=np.asarray(route_options(hip)),          # the option values every setting starts from
+                        **{'f_' + f: narrow(ans[:, :, k]) for k, f in enumerate(FIELDS)})
+    routes, counts = np.unique(ans.reshape(-1, len(FIELDS)), axis=0, return_counts=True)
+    print('%d cases x %d settings, %d distinct routes, %d bytes; by kernel:' % (len(table), len(SETTINGS), len(routes), os.path.getsize(path)))
+    for k in np.unique(ans[:, :, 0]):
+        print('  %-16s %d' % ('(refused)' if k < 0 else hip.CONV_KERNELS[k], int((ans[:, :, 0] == k).sum())))

@@ -6,7 +6,12 @@
 Per `.amdhsa_kernel` symbol the text from the symbol's label to its `.Lfunc_end` (instructions and the kernel descriptor with its
 register counts), comments stripped and the function index in local labels normalised, is hashed.  Prints how many kernels are
 identical under the same symbol, names the ones that differ or went, and lists the new ones with their register and spill counts
-(profiles/conv_route_split_notes.md describes the method; profiles/up_fold_notes.md uses it).  CPU only."""
+(profiles/conv_route_split_notes.md describes the method; profiles/up_fold_notes.md uses it).  CPU only.
+
+    python tools/kernel_asm_diff.py parent.s new.s --rename '(anonymous namespace)::ConvGeom=ConvGeom'
+
+compares under the DEMANGLED names after replacing OLD by NEW in the parent's: for a change that moves a kernel parameter's type to
+another namespace, which respells the symbols of the kernels that take it and nothing else (profiles/conv_route_unit_notes.md)."""
 import re, sys, hashlib, subprocess
 
 
@@ -26,6 +31,7 @@ def kernels(path):
             ln = re.sub(r'\.LBB%s_' % idx, '.LBB_', ln)
             ln = re.sub(r'\.Ltmp\d+', '.Ltmp', ln)
             lines.append(ln)
+        lines = [ln.replace(n, 'SELF') for ln in lines]
         out[n] = hashlib.sha1('\n'.join(lines).encode()).hexdigest()
         k = re.search(r'\.amdhsa_kernel\s+%s\n(.*?)\.end_amdhsa_kernel' % re.escape(n), txt, re.S).group(1)
         meta[n] = dict(vgpr=re.search(r'\.amdhsa_next_free_vgpr\s+(\d+)', k).group(1), accum=re.search(r'\.amdhsa_accum_offset\s+(\d+)', k).group(1))
@@ -43,6 +49,11 @@ def kernels(path):
 a, ma = kernels(sys.argv[1])
 b, mb = kernels(sys.argv[2])
 dem = lambda n: subprocess.run(['c++filt', n], capture_output=True, text=True).stdout.strip()
+if '--rename' in sys.argv:
+    old, new = sys.argv[sys.argv.index('--rename') + 1].split('=')
+    a = {dem(n).replace(old, new): h for n, h in a.items()}
+    b, mb = {dem(n): h for n, h in b.items()}, {dem(n): m for n, m in mb.items()}
+    dem = lambda n: n
 same = [n for n in a if n in b and a[n] == b[n]]
 diff = [n for n in a if n in b and a[n] != b[n]]
 print('parent kernels %d, new kernels %d, identical under the same symbol %d' % (len(a), len(b), len(same)))
