@@ -188,3 +188,74 @@ def sdf_to_mesh(sdf, level=0.02, render_all=False):
     k = bs if render_all else min(bs, 16)
     meshes = marching_cubes_batch(sdf[:k], level)
     return [v / n_cell - 0.5 for v, _ in meshes], [f for _, f in meshes]
+
+
+def mesh_to_sdf(meshes, n=64, trunc=0.2, fit=0.9, return_transform=False):
+    """Triangle meshes -> truncated SDF grids on the device (csrc/es_mesh_sdf.hip): the inverse of ``sdf_to_mesh``.
+
+    ``meshes``: a list of (verts [V,3] floating point, faces [T,3] integer with vertex ids local to the mesh) pairs of CUDA tensors --
+    what ``marching_cubes_batch`` returns -- or one such pair.  Returns float32 [K, 1, n, n, n], exactly what ``keep_sdfs=`` and
+    ``complete_sdfs=`` of the scene calls take: voxel (i, j, k) is the point (i/n - 0.5, j/n - 0.5, k/n - 0.5) (the normalisation of
+    ``sdf_to_mesh``: ``verts / n_cell - 0.5``), array axes are x, y, z, the value is the exact distance to the nearest triangle,
+    negative inside, clamped to [-trunc, trunc] (the reference clamps its grids to +-0.2, dataset/threedfront_dataset.py:313-317).
+    Inside is where the generalized winding number exceeds 0.5: the sign of a closed mesh, and a usable one for meshes with holes or
+    self-intersections.  Triangles of zero area are ignored.
+
+    ``fit=s`` (0 < s <= 1) centres each mesh on the bounding box of its vertices and scales it so that the longest side of the box is
+    ``s``, on the device.  The default 0.9 leaves 0.05 of margin (3.2 voxels at 64^3), enough for the 0.02 iso-level of
+    ``sdf_to_mesh``; it is THIS PACKAGE'S CHOICE, not the dataset's normalisation: the reference reads grids that a tool outside it
+    wrote, and fits generated meshes to their layout boxes afterwards anyway.  ``fit=None`` takes the coordinates as they are.
+    ``return_transform=True`` also returns float32 [K, 4]: centre x, y, z and scale of each mesh, fitted = (v - centre) * scale.
+
+    Every refusal of the arguments is a ValueError raised before any device work; a face index outside its mesh is caught on the
+    device (never dereferenced) and raised as a ValueError after the call."""
+    if isinstance(meshes, tuple) and len(meshes) == 2 and torch.is_tensor(meshes[0]):
+        meshes = [meshes]
+    if not isinstance(meshes, (list, tuple)) or len(meshes) == 0:
+        raise ValueError('mesh_to_sdf: expects a non-empty list of (verts, faces) pairs')
+    if not isinstance(n, (int, np.integer)) or isinstance(n, bool) or n < 2:
+        raise ValueError('mesh_to_sdf: n must be an integer >= 2, got %r' % (n,))
+    n = int(n)
+    if not trunc > 0:
+        raise ValueError('mesh_to_sdf: trunc must be positive, got %r' % (trunc,))
+    if fit is not None and not 0 < fit <= 1:
+        raise ValueError('mesh_to_sdf: fit must be in (0, 1] (or None: coordinates as given), got %r' % (fit,))
+    K = len(meshes)
+    if K * n ** 3 >= 2 ** 31:
+        raise ValueError('mesh_to_sdf: %d grids of %d^3 are beyond int32 indexing' % (K, n))
+    dev = None
+    for k, mesh in enumerate(meshes):
+        if not (isinstance(mesh, (list, tuple)) and len(mesh) == 2 and torch.is_tensor(mesh[0]) and torch.is_tensor(mesh[1])):
+            raise ValueError('mesh_to_sdf: mesh %d is not a (verts, faces) pair of tensors' % k)
+        v, f = mesh
+        if not (v.dim() == 2 and v.shape[1] == 3 and v.is_floating_point()):
+            raise ValueError('mesh_to_sdf: verts of mesh %d must be a floating-point tensor [V, 3], got %s %s' % (k, v.dtype, tuple(v.shape)))
+        if not (f.dim() == 2 and f.shape[1] == 3 and f.dtype in (torch.int32, torch.int64)):
+            raise ValueError('mesh_to_sdf: faces of mesh %d must be an int32 / int64 tensor [T, 3], got %s %s' % (k, f.dtype, tuple(f.shape)))
+        if f.shape[0] == 0 or v.shape[0] == 0:
+            raise ValueError('mesh_to_sdf: mesh %d has no %s' % (k, 'faces' if f.shape[0] == 0 else 'vertices'))
+    for k, (v, f) in enumerate(meshes):
+        if not (v.is_cuda and f.is_cuda):
+            raise ValueError('mesh_to_sdf: mesh %d is not on the device (CUDA tensors expected)' % k)
+        dev = v.device if dev is None else dev
+        if v.device != dev or f.device != dev:
+            raise ValueError('mesh_to_sdf: mesh %d is on %s / %s, the first mesh on %s' % (k, v.device, f.device, dev))
+    vofs = np.cumsum([0] + [int(m[0].shape[0]) for m in meshes])
+    tofs = np.cumsum([0] + [int(m[1].shape[0]) for m in meshes])
+    L = hip.lib()
+    with torch.cuda.device(dev):
+        verts = torch.cat([m[0].float() for m in meshes]).contiguous()
+        # (an int64 id beyond int32 stays out of range after the cast)
+        faces = torch.cat([m[1].clamp(-1, 2 ** 31 - 1).int() if m[1].dtype == torch.int64 else m[1] for m in meshes]).contiguous()
+        vo, to = torch.from_numpy(vofs).to(dev), torch.from_numpy(tofs).to(dev)
+        ws = torch.empty(L.es_mesh_sdf_workspace(K, int(tofs[-1])), dtype=torch.uint8, device=dev)
+        bad = torch.empty(K, dtype=torch.int32, device=dev)
+        tf = torch.empty(K, 4, dtype=torch.float32, device=dev)
+        out = torch.empty(K, 1, n, n, n, dtype=torch.float32, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        hip.check(L.es_mesh_sdf(p(verts), p(faces), p(vo), p(to), K, int(vofs[-1]), int(tofs[-1]), n, float(trunc),
+                                0.0 if fit is None else float(fit), p(ws), p(bad), p(tf), p(out), hip.current_stream()), 'es_mesh_sdf')
+        flagged = bad.cpu().nonzero().flatten().tolist()
+    if flagged:
+        raise ValueError('mesh_to_sdf: meshes %s have a face index outside [0, V)' % flagged)
+    return (out, tf) if return_transform else out

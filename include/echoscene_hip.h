@@ -681,6 +681,27 @@ int es_marching_cubes_emit(const float* sdf, int O, int n, float level, const in
                            const int64_t* vert_offset, const int64_t* tri_offset, float* verts, int32_t* faces,
                            es_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh -> truncated SDF (csrc/es_mesh_sdf.hip): the inverse of the marching cubes above, so that a caller with a triangle mesh gets
+ * the grids the shape-keeping / shape-completing calls take.  The reference only reads precomputed grids
+ * (dataset/threedfront_dataset.py:313-317, clamped to +-0.2); the tool that wrote them is not part of it.
+ * K meshes packed the way the emit call above writes them: verts [total_V, 3] fp32, faces [total_T, 3] int32 with vertex ids local
+ * to the mesh, vert_offset / tri_offset device int64[K + 1] (first row of each mesh, then the totals).
+ * sdf [K, n, n, n] fp32: voxel (i, j, k) is the point (i/n - 0.5, j/n - 0.5, k/n - 0.5), array axes x, y, z; the value is the exact
+ * distance to the nearest triangle, negative where the generalized winding number exceeds 0.5, clamped to [-trunc, trunc].
+ * Brute force over all triangles in their order: no atomics, the same bits on every run and for every batch a mesh is part of.
+ * fit > 0: each mesh is first centred on the bounding box of its vertices and scaled so that the longest side of the box is `fit`;
+ * fit <= 0: the vertices are cube coordinates already.  transform (optional, [K, 4] fp32): centre x, y, z and scale of each mesh,
+ * fitted = (v - centre) * scale (0, 0, 0, 1 without a fit).  Triangles of zero area contribute nothing.
+ * A face index outside its mesh is never dereferenced: it is clamped and bad_flags[mesh] (device int32[K], written by every call:
+ * 0 or 1) is raised; the grid of such a mesh is not meaningful.  workspace: the number of bytes the workspace query returns for
+ * (K, total_T), 16-byte aligned.  Every argument is checked on the host before anything is enqueued.
+ * ---------------------------------------------------------------------------------------- */
+size_t es_mesh_sdf_workspace(int K, long total_T);
+int es_mesh_sdf(const float* verts, const int32_t* faces, const int64_t* vert_offset, const int64_t* tri_offset, int K,
+                long total_V, long total_T, int n, float trunc, float fit, void* workspace, int32_t* bad_flags,
+                float* transform, float* sdf, es_stream stream);
+
 /* library-wide one-off device allocations (zero page); call once outside stream capture */
 int es_init(void);
 /* The sampling loops.  `step` is the device scalar the plan's ops read; it is set to first_step,
