@@ -702,6 +702,26 @@ int es_mesh_sdf(const float* verts, const int32_t* faces, const int64_t* vert_of
                 long total_V, long total_T, int n, float trunc, float fit, void* workspace, int32_t* bad_flags,
                 float* transform, float* sdf, es_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Shape-set metrics (csrc/es_shape_metrics.hip): what the reference's scripts/compute_mmd_cov_1nn.py needs on the device.
+ * es_chamfer_matrix: a [Na, P, 3], b [Nb, Q, 3] fp32 -> out [Na, Nb] fp32,
+ *   out[i, j] = mean_p min_q |a_ip - b_jq|^2 + mean_q min_p |a_ip - b_jq|^2   (the reference's dl.mean(1) + dr.mean(1)).
+ * One workgroup per pair computes both directions and writes the entry once: an entry's bits depend on its two clouds alone (not on
+ * the run, the other clouds of the call or the order of the arguments: out(a, b)[i, j] and out(b, a)[j, i] are equal).
+ * symmetric != 0: b must be a (same pointer and counts); only pairs i < j are computed and mirrored, the diagonal is exactly 0.
+ * Distances are the expanded form xx + yy - 2 xy in fp32 (the reference's distChamfer) on the fp32 matrix instruction; each
+ * nearest-neighbour distance is clamped at 0 before it is summed (in double).  The form cancels far from the origin: the clouds are
+ * expected normalised as es_cloud_normalize leaves them (centred, max |coordinate| = 1).
+ * es_cloud_normalize: the reference's normalization after sample_pc.  verts [total_V, 3] fp32, vert_offset device int64[K + 1],
+ * index device int32[K, number] (vertex ids local to the cloud) -> out [K, number, 3] fp32: the gathered points minus their mean per
+ * axis, divided by the largest absolute coordinate of the centred cloud (in double, rounded once).  A cloud whose points all coincide
+ * is 0 / 0 = NaN, as in the reference.  An index outside its cloud is never dereferenced: it is clamped and bad_flags[cloud] (device
+ * int32[K], written by every call: 0 or 1) is raised.  Every argument is checked on the host before anything is enqueued.
+ * ---------------------------------------------------------------------------------------- */
+int es_chamfer_matrix(const float* a, int Na, int P, const float* b, int Nb, int Q, int symmetric, float* out, es_stream stream);
+int es_cloud_normalize(const float* verts, const int64_t* vert_offset, const int32_t* index, int K, int number, long total_V,
+                       int32_t* bad_flags, float* out, es_stream stream);
+
 /* library-wide one-off device allocations (zero page); call once outside stream capture */
 int es_init(void);
 /* The sampling loops.  `step` is the device scalar the plan's ops read; it is set to first_step,
