@@ -257,6 +257,10 @@ EXPORTS = {
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'es_chamfer_matrix': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'es_cloud_normalize': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'es_emd_matrix': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'es_emd_matrix_rounds': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
+    'es_emd_max_points': (C.c_int, []),
     'es_plan_create': (C.c_void_p, [C.POINTER(Op), C.c_int]),
     'es_plan_destroy': (None, [C.c_void_p]),
     'es_plan_num_ops': (C.c_int, [C.c_void_p]),

@@ -1,12 +1,14 @@
 """Shape-set metrics of the reference's ``scripts/compute_mmd_cov_1nn.py`` on the device -- SURVEY.md section 8(f) rank 4: generated
 SDF -> mesh (``postprocess.marching_cubes_batch``) -> point cloud (``point_clouds``) -> matrix of Chamfer distances
-(``pairwise_chamfer``, csrc/es_shape_metrics.hip) -> MMD, COV and 1-NN accuracy (``compute_all_metrics``).  The matrix is the expensive
-part and stays on the device; the N x N statistics after it are bookkeeping and run in numpy on one copy of the three matrices.
+(``pairwise_chamfer``, csrc/es_shape_metrics.hip) and of earth mover's distances (``pairwise_emd``, csrc/es_emd.hip) -> MMD, COV and
+1-NN accuracy by either distance (``compute_all_metrics``).  The matrices are the expensive part and stay on the device; the N x N
+statistics after them are bookkeeping and run in numpy on one copy of the matrices.
 
 ``lgan_mmd_cov``, ``knn`` and ``compute_all_metrics`` take the call shapes of the reference's functions of those names and return the
 same keys; they are written from the formulas (Achlioptas et al. 2018 for MMD / COV, Lopez-Paz & Oquab 2017 for the 1-NN two-sample
-test).  The EMD entries are NOT computed: the reference's fast EMD is an extension outside its tree and its fallback is an assignment
-solver on the host."""
+test).  The six EMD entries are computed on request (``emd=True``): they are the values of the reference's exact route (``emd_approx``,
+an assignment solver on the host, once per pair) within ``EMD_EPS`` per matrix entry, from an auction kernel that solves one pair per
+workgroup; the approximate values of the reference's accelerated route, an extension outside its tree, are not reproduced."""
 import ctypes as C
 import numpy as np
 import torch
@@ -14,6 +16,18 @@ import torch
 from . import hip
 
 _CD_KEYS = ('lgan_mmd-CD', 'lgan_cov-CD', 'lgan_mmd_smp-CD', '1-NN-CD-acc_t', '1-NN-CD-acc_f', '1-NN-CD-acc')
+_EMD_KEYS = tuple(k.replace('CD', 'EMD') for k in _CD_KEYS)
+
+# |pairwise_emd - exact optimum| per entry for clouds whose joint bounding box has every extent below 4 (normalised clouds: at most 2);
+# the derivation is in the header of csrc/es_emd.hip.  Larger clouds: times 2^(e - 3), e the scale exponent derived there.
+EMD_EPS = 4e-6
+
+
+def __getattr__(name):
+    if name == 'EMD_MAX_POINTS':                                    # read from the library on first use, a plain attribute from then on
+        globals()[name] = int(hip.lib().es_emd_max_points())
+        return globals()[name]
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))
 
 
 def sample_indices(n, number=5000):
@@ -87,9 +101,9 @@ def _normalize(verts, vofs, index, who):
     return out
 
 
-def _check_sets(who, squares, **sets):
-    """the refusals shared by the calls that take sets of clouds, in the order: tensor, floating point, [N, P, 3], int32, one device, CUDA
-    (``squares``: each set is also paired with itself)"""
+def _check_sets(who, squares, emd=False, **sets):
+    """the refusals shared by the calls that take sets of clouds, in the order: tensor, floating point, [N, P, 3], int32, (``emd``: equal
+    point counts, at most EMD_MAX_POINTS,) one device, CUDA (``squares``: each set is also paired with itself)"""
     for name, x in sets.items():
         if not torch.is_tensor(x):
             raise ValueError('%s: %s must be a tensor [N, P, 3], got %s' % (who, name, type(x).__name__))
@@ -100,6 +114,15 @@ def _check_sets(who, squares, **sets):
         if x.shape[0] * x.shape[1] * 3 >= 2 ** 31:
             raise ValueError('%s: %s with %d x %d x 3 coordinates is beyond int32 indexing' % (who, name, x.shape[0], x.shape[1]))
     xs = list(sets.items())
+    if emd:
+        for name, x in xs[1:]:
+            if x.shape[1] != xs[0][1].shape[1]:
+                raise ValueError('%s: the earth mover\'s distance needs equal point counts, %s has %d points per cloud and %s %d'
+                                 % (who, xs[0][0], xs[0][1].shape[1], name, x.shape[1]))
+        most = globals().get('EMD_MAX_POINTS') or __getattr__('EMD_MAX_POINTS')
+        if xs[0][1].shape[1] > most:
+            raise ValueError('%s: %d points per cloud, the earth mover\'s distance takes at most EMD_MAX_POINTS = %d'
+                             % (who, xs[0][1].shape[1], most))
     for name, x in xs[1:]:
         if x.device != xs[0][1].device:
             raise ValueError('%s: %s is on %s and %s on %s (different devices)' % (who, xs[0][0], xs[0][1].device, name, x.device))
@@ -142,6 +165,56 @@ def _chamfer_matrix(a, b):
         p = lambda t: C.c_void_p(t.data_ptr())
         hip.check(hip.lib().es_chamfer_matrix(p(a), a.shape[0], a.shape[1], p(b), b.shape[0], b.shape[1], 1 if sym else 0, p(out),
                                               hip.current_stream()), 'es_chamfer_matrix')
+    return out
+
+
+def pairwise_emd(a, b=None):
+    """The matrix of earth mover's distances between every cloud of ``a`` [Na, P, 3] and every cloud of ``b`` [Nb, P, 3] (floating-point
+    CUDA tensors with the same P, at most ``EMD_MAX_POINTS``): float32 [Na, Nb] on the device, ``out[i, j]`` = the minimum over
+    one-to-one matchings sigma of ``mean_p |a_ip - b_j,sigma(p)|`` (Euclidean), the value of the reference's ``emd_approx``, within
+    ``EMD_EPS`` of the exact optimum.  ``b=None`` is one set against itself: half the pairs are computed and mirrored, and the
+    diagonal is exactly 0.
+
+    One workgroup per pair runs an integer auction (csrc/es_emd.hip): an entry's bits depend on its two clouds and their order alone,
+    so a matrix equals the matrices of its parts and runs repeat; ``pairwise_emd(a, b)`` and ``pairwise_emd(b, a).T`` agree within the
+    guarantee, not bit for bit (bidders and objects differ).  Distances are direct differences: the clouds need not be normalised.
+    Every refusal of the arguments is a ValueError raised before any device work; a pair with a non-finite coordinate, or one that
+    reached the kernel's cap on bidding rounds, raises a RuntimeError that names the pairs."""
+    if b is None:
+        _check_sets('pairwise_emd', True, emd=True, a=a)
+    else:
+        _check_sets('pairwise_emd', False, emd=True, a=a, b=b)
+    return _raise_on_status('pairwise_emd', *_emd_matrix(a, b))
+
+
+def _emd_matrix(a, b, rounds=False):
+    """es_emd_matrix on checked arguments; b None: the symmetric mode.  (out, status[, rounds]) on the device"""
+    with torch.cuda.device(a.device):
+        a = a.float().contiguous()
+        sym = b is None
+        b = a if sym else b.float().contiguous()
+        out = torch.empty(a.shape[0], b.shape[0], dtype=torch.float32, device=a.device)
+        status = torch.empty(a.shape[0], b.shape[0], dtype=torch.int32, device=a.device)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        if rounds:
+            nr = torch.empty_like(status)
+            hip.check(hip.lib().es_emd_matrix_rounds(p(a), a.shape[0], p(b), b.shape[0], a.shape[1], 1 if sym else 0, p(out), p(status),
+                                                     p(nr), hip.current_stream()), 'es_emd_matrix_rounds')
+            return out, status, nr
+        hip.check(hip.lib().es_emd_matrix(p(a), a.shape[0], p(b), b.shape[0], a.shape[1], 1 if sym else 0, p(out), p(status),
+                                          hip.current_stream()), 'es_emd_matrix')
+    return out, status
+
+
+def _raise_on_status(who, out, *status):
+    """out, unless a pair of one of the status matrices is flagged"""
+    for st in status:
+        st = st.cpu().numpy()
+        for code, what in ((2, 'have a coordinate that is not finite (or span 2^61 or more)'),
+                           (1, 'reached the cap on bidding rounds (no result; please report the clouds)')):
+            pairs = np.argwhere(st == code)
+            if len(pairs):
+                raise RuntimeError('%s: pairs %s %s' % (who, [tuple(int(v) for v in ij) for ij in pairs[:8]] + (['...'] if len(pairs) > 8 else []), what))
     return out
 
 
@@ -212,18 +285,36 @@ def metrics_from_matrices(M_rs, M_rr, M_ss):
     return dict(zip(_CD_KEYS, (mmd, cov, mmd_smp, nn1['acc_t'], nn1['acc_f'], nn1['acc'])))
 
 
-def compute_all_metrics(sample_pcs, ref_pcs, batch_size=None, accelerated_cd=True):
+def emd_metrics_from_matrices(M_rs, M_rr, M_ss):
+    """The six EMD entries of ``compute_all_metrics`` from the three EMD matrices: the same statistics under the reference's EMD keys."""
+    return dict(zip(_EMD_KEYS, metrics_from_matrices(M_rs, M_rr, M_ss).values()))
+
+
+def _three(M_rs, M_rr, M_ss):
+    """the three device matrices as numpy after one copy"""
+    nr, ns = M_rr.shape[0], M_ss.shape[0]
+    host = torch.cat([M_rs.flatten(), M_rr.flatten(), M_ss.flatten()]).cpu().numpy()
+    return (host[:nr * ns].reshape(nr, ns), host[nr * ns:nr * ns + nr * nr].reshape(nr, nr), host[nr * ns + nr * nr:].reshape(ns, ns))
+
+
+def compute_all_metrics(sample_pcs, ref_pcs, batch_size=None, accelerated_cd=True, emd=False):
     """MMD-CD, COV-CD and the 1-NN accuracy (CD) of a set of generated clouds [N_sample, P, 3] against a set of reference clouds
     [N_ref, Q, 3], as the reference's ``compute_all_metrics``: {'lgan_mmd-CD', 'lgan_cov-CD', 'lgan_mmd_smp-CD', '1-NN-CD-acc_t',
     '1-NN-CD-acc_f', '1-NN-CD-acc'}, 0-dim float32 tensors on the clouds' device.  The three matrices M_rs, M_rr, M_ss come from
-    ``pairwise_chamfer`` (the last two in its symmetric mode); the statistics run on the host after one copy.  The six EMD entries of
-    the reference are left out (see the module's docstring).  ``batch_size`` and ``accelerated_cd`` are accepted and ignored: the
-    matrix kernel needs no batching and is the only route."""
-    _check_sets('compute_all_metrics', True, sample_pcs=sample_pcs, ref_pcs=ref_pcs)
-    M_rs = _chamfer_matrix(ref_pcs, sample_pcs)
-    M_rr = _chamfer_matrix(ref_pcs, None)
-    M_ss = _chamfer_matrix(sample_pcs, None)
-    nr, ns = M_rr.shape[0], M_ss.shape[0]
-    host = torch.cat([M_rs.flatten(), M_rr.flatten(), M_ss.flatten()]).cpu().numpy()
-    return _scalars(metrics_from_matrices(host[:nr * ns].reshape(nr, ns), host[nr * ns:nr * ns + nr * nr].reshape(nr, nr),
-                                          host[nr * ns + nr * nr:].reshape(ns, ns)), sample_pcs)
+    ``pairwise_chamfer`` (the last two in its symmetric mode); the statistics run on the host after one copy.
+
+    ``emd=True`` (Q must equal P, at most ``EMD_MAX_POINTS``) returns the reference's twelve keys in its order: the three ``lgan_*-CD``,
+    the three ``lgan_*-EMD``, the three ``1-NN-CD-*``, the three ``1-NN-EMD-*``; the EMD entries are the same statistics of the three
+    matrices of ``pairwise_emd``.  ``batch_size`` and ``accelerated_cd`` are accepted and ignored: the matrix kernels need no
+    batching and are the only route."""
+    _check_sets('compute_all_metrics', True, emd=bool(emd), sample_pcs=sample_pcs, ref_pcs=ref_pcs)
+    cd = metrics_from_matrices(*_three(_chamfer_matrix(ref_pcs, sample_pcs), _chamfer_matrix(ref_pcs, None), _chamfer_matrix(sample_pcs, None)))
+    if not emd:
+        return _scalars(cd, sample_pcs)
+    (E_rs, s_rs), (E_rr, s_rr), (E_ss, s_ss) = _emd_matrix(ref_pcs, sample_pcs), _emd_matrix(ref_pcs, None), _emd_matrix(sample_pcs, None)
+    _raise_on_status('compute_all_metrics (ref x sample)', E_rs, s_rs)
+    _raise_on_status('compute_all_metrics (ref x ref)', E_rr, s_rr)
+    _raise_on_status('compute_all_metrics (sample x sample)', E_ss, s_ss)
+    em = emd_metrics_from_matrices(*_three(E_rs, E_rr, E_ss))
+    both = list(cd.items())[:3] + list(em.items())[:3] + list(cd.items())[3:] + list(em.items())[3:]
+    return _scalars(dict(both), sample_pcs)

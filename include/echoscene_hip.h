@@ -722,6 +722,26 @@ int es_chamfer_matrix(const float* a, int Na, int P, const float* b, int Nb, int
 int es_cloud_normalize(const float* verts, const int64_t* vert_offset, const int32_t* index, int K, int number, long total_V,
                        int32_t* bad_flags, float* out, es_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Earth mover's distance (csrc/es_emd.hip): the EMD matrix of the same script (its emd_approx, one assignment problem per pair).
+ * es_emd_matrix: a [Na, P, 3], b [Nb, P, 3] fp32, the same P -> out [Na, Nb] fp32,
+ *   out[i, j] = min over one-to-one matchings sigma of mean_p |a_ip - b_j,sigma(p)|      (Euclidean, from direct differences).
+ * One workgroup per pair runs an integer eps-scaling auction on costs quantised to 2^-20 (for clouds whose joint bounding box has
+ * every extent below 4; coarser by powers of two beyond).  Guarantee: |out - optimum| <= 4e-6 for such clouds (4e-6 * 2^(e - 3) in
+ * general, e as derived in the source file).  An entry's bits depend on its two clouds and their order alone; out(a, b)[i, j] and
+ * out(b, a)[j, i] agree within the guarantee, not bit for bit.  symmetric != 0: b must be a (same pointer and count); pairs i < j
+ * are computed and mirrored, the diagonal is exactly 0 (status 0).
+ * status [Na, Nb] device int32, written for every entry: 0 fine; 1 the pair reached the hard cap on bidding rounds (out is NaN);
+ * 2 a coordinate is not finite or the clouds span 2^61 or more (out is NaN; nothing is iterated on).
+ * es_emd_matrix_rounds: the same call with rounds [Na, Nb] device int32 (NULL: not wanted), the bidding rounds each pair took.
+ * es_emd_max_points: the largest P (the state of a pair lives in the LDS of one CU).
+ * Every argument is checked on the host before anything is enqueued.
+ * ---------------------------------------------------------------------------------------- */
+int es_emd_matrix(const float* a, int Na, const float* b, int Nb, int P, int symmetric, float* out, int32_t* status, es_stream stream);
+int es_emd_matrix_rounds(const float* a, int Na, const float* b, int Nb, int P, int symmetric, float* out, int32_t* status,
+                         int32_t* rounds, es_stream stream);
+int es_emd_max_points(void);
+
 /* library-wide one-off device allocations (zero page); call once outside stream capture */
 int es_init(void);
 /* The sampling loops.  `step` is the device scalar the plan's ops read; it is set to first_step,

@@ -9,10 +9,18 @@ is the window over its count.  The matrices must agree within the bar of the GPU
 tests/golden/shape_metrics.npz).  Prints point pairs per second (2 N^2 P^2 per matrix) and the share of the fp32 matrix peak the
 matrix kernel reaches (8 flop per pair with K = 4; 157.3 TFLOP/s).
 
-  python tools/shape_metrics_times.py [--n 128] [--points 2048] [--window 1.0] [--rounds 3] [--out FILE]"""
+With --emd-n N the matrix of earth mover's distances is timed too (shape_metrics.pairwise_emd, es_emd_matrix: one workgroup per
+pair, an integer auction): N x N clouds of --emd-points points, a warm-up call on two clouds of that size and then --emd-calls calls
+of the full matrix between device events, each reported; with them the bidding rounds the pairs took, the time of the symmetric
+mode, and -- where scipy can be imported -- what the host route costs per pair on the same clouds: the reference's emd_approx step,
+linear_sum_assignment on the fp32 distance matrix, over --host-pairs pairs, whose values the kernel must match within EMD_EPS.
+
+  python tools/shape_metrics_times.py [--n 128] [--points 2048] [--window 1.0] [--rounds 3] [--out FILE]
+                                      [--emd-n 128] [--emd-points 2048] [--emd-calls 2] [--host-pairs 2] [--no-cd]"""
 import argparse
 import os
 import sys
+import time
 
 import numpy as np
 import torch
@@ -20,7 +28,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from echoscene_amd.chamfer import chamferDist                       # noqa: E402
-from echoscene_amd.shape_metrics import pairwise_chamfer            # noqa: E402
+from echoscene_amd.shape_metrics import EMD_EPS, _emd_matrix, pairwise_chamfer, pairwise_emd          # noqa: E402
 
 
 def clouds(N, P, seed):
@@ -61,6 +69,49 @@ def window(fn, seconds):
             return e0.elapsed_time(e1) / calls, calls
 
 
+def timed(fn):
+    """one call between device events: (result, ms)"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    out = fn()
+    e1.record()
+    e1.synchronize()
+    return out, e0.elapsed_time(e1)
+
+
+def emd_lines(N, P, calls, host_pairs):
+    a, b = clouds(N, P, 1), clouds(N, P, 2)
+    pairwise_emd(a[:1], b[:1])                                      # (the warm-up call: code object, LDS attribute)
+    torch.cuda.synchronize()
+    lines = ['EMD: %d x %d clouds of %d points' % (N, N, P)]
+    for c in range(calls):
+        m, ms = timed(lambda: pairwise_emd(a, b))
+        lines.append('call %d matrix    %10.1f ms, %8.3f ms per pair; entries %.4f .. %.4f' % (c, ms, ms / (N * N), m.min().item(), m.max().item()))
+    _, ms = timed(lambda: pairwise_emd(a))
+    lines.append('symmetric mode (one set against itself, %d pairs): %.1f ms' % (N * (N - 1) // 2, ms))
+    (m2, status, rounds), _ = timed(lambda: _emd_matrix(a, b, rounds=True))
+    assert torch.equal(m2, m) and not status.any().item()           # runs repeat bit for bit
+    r = rounds.double()
+    lines.append('bidding rounds per pair: median %.0f, largest %.0f (%.2f P); one pair alone: %.1f ms'
+                 % (r.median().item(), r.max().item(), r.max().item() / P, timed(lambda: pairwise_emd(a[:1], b[:1]))[1]))
+    try:
+        from scipy.optimize import linear_sum_assignment
+    except ImportError:
+        lines.append('host route: scipy cannot be imported here, not measured')
+        return lines
+    host_ms, worst = [], 0.0
+    for k in range(host_pairs):
+        d = (a[k].cpu()[:, None, :] - b[k].cpu()[None, :, :]).norm(dim=-1).numpy()      # the reference's emd_approx on the CPU
+        t0 = time.perf_counter()
+        rows, cols = linear_sum_assignment(d)
+        host_ms.append(1e3 * (time.perf_counter() - t0))
+        worst = max(worst, abs(float(d[rows, cols].mean()) - m[k, k].item()))
+    lines.append('host route (linear_sum_assignment on the fp32 distances, this machine\'s CPU): %s ms per pair; max |kernel - host| = %.3g '
+                 '(EMD_EPS %.3g)' % (', '.join('%.0f' % h for h in host_ms), worst, EMD_EPS))
+    assert worst <= EMD_EPS + 4e-7, lines[-1]                        # (the host value carries its own fp32 rounding)
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--n', type=int, default=128)
@@ -68,7 +119,23 @@ def main():
     ap.add_argument('--window', type=float, default=1.0)
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--out', default='')
+    ap.add_argument('--emd-n', type=int, default=0, help='also time the EMD matrix of this many clouds a side (0: no)')
+    ap.add_argument('--emd-points', type=int, default=2048)
+    ap.add_argument('--emd-calls', type=int, default=2)
+    ap.add_argument('--host-pairs', type=int, default=2)
+    ap.add_argument('--no-cd', action='store_true', help='skip the Chamfer part')
     args = ap.parse_args()
+    text = '' if args.no_cd else cd_text(args)
+    if args.emd_n > 0:
+        text += ('\n' if text else 'device: %s\n' % torch.cuda.get_device_name(0)) + \
+            '\n'.join(emd_lines(args.emd_n, args.emd_points, args.emd_calls, args.host_pairs))
+    print(text)
+    if args.out:
+        with open(args.out, 'w') as fp:
+            fp.write(text + '\n')
+
+
+def cd_text(args):
     N, P = args.n, args.points
     bar = 4 * float(np.load(os.path.join(ROOT, 'tests', 'golden', 'shape_metrics.npz'))['ref_fp32_err'])
     a, b = clouds(N, P, 1), clouds(N, P, 2)
@@ -90,11 +157,7 @@ def main():
                  % (new, old, old / new, 100 * pairs * 8 / (new * 1e-3) / 157.3e12))
     ms_sym, _ = window(lambda: pairwise_chamfer(a), args.window)
     lines.append('symmetric mode (one set against itself): %.3f ms' % ms_sym)
-    text = '\n'.join(lines)
-    print(text)
-    if args.out:
-        with open(args.out, 'w') as fp:
-            fp.write(text + '\n')
+    return '\n'.join(lines)
 
 
 if __name__ == '__main__':
