@@ -742,6 +742,34 @@ int es_emd_matrix_rounds(const float* a, int Na, const float* b, int Nb, int P, 
                          int32_t* rounds, es_stream stream);
 int es_emd_max_points(void);
 
+/* ------------------------------------------------------------------------------------------
+ * Layout metrics (csrc/es_layout_metrics.hip): the scene-graph constraint accuracy of the reference's helpers/metrics_3dfront.py
+ * (validate_constrains, validate_constrains_changes, box3d_iou), a whole test set per launch, one thread per triple or pair.
+ * Boxes are rows (l, h, w, px, py, pz[, ...]) fp32: l along z, h along y, w along x, (px, py, pz) the bottom centre; further columns
+ * are ignored (no rotation, as in the reference).
+ * es_relation_check: boxes [O, ld >= 6], triples [T, 3] device int64 (s, p, o), rule_of_pred device int8[n_pred] (the rule of each
+ *   predicate id; -1: none).  Rules: 0 left, 1 right, 2 front, 3 behind, 4 smaller, 5 bigger, 6 shorter, 7 taller, 8 standing on,
+ *   9 close by, 10 symmetrical to.  keep (NULL: none) is a device mask [O] of keep_dtype 0 fp32, 1 int64, 2 one byte, 3 int32;
+ *   keep_mode 0: every triple, 1: only triples with keep == 1 at both ends, 2: only triples with keep == 0 at an end.
+ *   strict != 0: left / right / front / behind also fail when box3d_iou(s, o) > overlap_threshold.
+ *   -> rule device int8[T]: the rule that applied, -1 for a predicate without one, a triple left out by keep, or a bad index;
+ *      ok device int8[T]: 1 fulfilled, 0 not (0 where rule is -1);
+ *      counts (NULL: not wanted) device int32[11][2]: per rule, triples fulfilled and triples evaluated (zeroed by the call);
+ *      status device int32, written by every call: bit 0 a node index outside [0, O), bit 1 a predicate outside [0, n_pred); nothing is
+ *      read through such an index.
+ *   The fp32 rules are evaluated in fp32 and the corner rules (the IoU, close by) in double, operation by operation as numpy 2
+ *   evaluates the reference on float32 boxes; counts are integer atomics: the outputs repeat bit for bit.
+ * es_box3d_iou: K pairs of rows a [K, lda >= 6], b [K, ldb >= 6] -> iou [K], iou_2d [K] device double: the intersection volume over the
+ *   smaller volume, and the intersection over the union of the footprints.  with_translation == 0: both boxes centred at the origin.
+ *   A flat or negatively wound box b, or touching boxes, intersect in nothing; a zero volume gives 0 / 0 = NaN.
+ * Every argument is checked on the host before anything is enqueued.
+ * ---------------------------------------------------------------------------------------- */
+int es_relation_check(const float* boxes, int O, int ld, const int64_t* triples, int T, const int8_t* rule_of_pred, int n_pred,
+                      const void* keep, int keep_dtype, int keep_mode, int strict, double overlap_threshold, int8_t* rule, int8_t* ok,
+                      int32_t* counts, int32_t* status, es_stream stream);
+int es_box3d_iou(const float* a, int lda, const float* b, int ldb, int K, int with_translation, double* iou, double* iou_2d,
+                 es_stream stream);
+
 /* library-wide one-off device allocations (zero page); call once outside stream capture */
 int es_init(void);
 /* The sampling loops.  `step` is the device scalar the plan's ops read; it is set to first_step,
