@@ -770,6 +770,33 @@ int es_relation_check(const float* boxes, int O, int ld, const int64_t* triples,
 int es_box3d_iou(const float* a, int lda, const float* b, int ldb, int K, int with_translation, double* iou, double* iou_2d,
                  es_stream stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Scene metrics (csrc/es_scene_metrics.hip): the point-cloud overlap between placed objects of the reference's
+ * helpers/metrics_3dfront.py (pointcloud_overlap, pointcloud_overlap_pair) and the fit of helpers/util.py (fit_shapes_to_box).
+ * Clouds are fp32 [O, P, 3], contiguous, one P for a call.  Everything is fp32 with one rounding per operation.
+ * es_cloud_fit: one workgroup per object.  boxes [O, ld] rows (size x, y, z, centre x, y, z[, angle in degrees]), ld >= 7 with
+ *   withangle != 0 and >= 6 without.  Per axis: p / (max - min over the cloud) * size; then the rotation by the angle, up == 0 about z
+ *   (x' = c x - s y, y' = s x + c y), up == 1 about y (x' = c x - s z, z' = s x + c z), c and s the correctly rounded fp32 cosine and
+ *   sine of the fp32 radians; then + centre.
+ *   -> placed [O, P, 3]; bounds [O, 6] (lo x, y, z, hi x, y, z of the placed values); status device int32[O], written for every object:
+ *      bit 0 an axis of zero extent, bit 1 a coordinate, box entry or result that is not finite.
+ *   boxes NULL: the clouds are taken as placed (placed may be NULL): bounds and status bit 1 only.
+ * es_cloud_self_nn: d11 [O, P], the squared distance dx*dx + dy*dy + dz*dz from each point to the nearest point of the same cloud with
+ *   another index; +inf for P == 1.
+ * es_cloud_overlap: pairs [K, 2] device int32 (first cloud: an index into qclouds [Oq, Pq, 3], with d11 [Oq, Pq] its self distances;
+ *   second cloud: an index into cclouds [Oc, Pc, 3], with cbounds [Oc, 6] its bounds; both sets may be the same buffer).
+ *   -> counts device int32[K] (zeroed by the call): the points of the first cloud with a point of the second strictly nearer than
+ *      d11 (compared as squares; on a tie the own cloud wins).  A query whose squared distance to the bounds of the second cloud is
+ *      >= its d11 is decided without a look at the second cloud.  Integer atomics: a count depends on its two clouds alone.
+ *      status device int32, written by every call: bit 0 a pair index outside [0, Oq) x [0, Oc); nothing is read through it.
+ * Every argument is checked on the host before anything is enqueued.
+ * ---------------------------------------------------------------------------------------- */
+int es_cloud_fit(const float* clouds, int O, int P, const float* boxes, int ld, int withangle, int up, float* placed, float* bounds,
+                 int32_t* status, es_stream stream);
+int es_cloud_self_nn(const float* clouds, int O, int P, float* d11, es_stream stream);
+int es_cloud_overlap(const float* qclouds, int Oq, int Pq, const float* d11, const float* cclouds, int Oc, int Pc, const float* cbounds,
+                     const int32_t* pairs, int K, int32_t* counts, int32_t* status, es_stream stream);
+
 /* library-wide one-off device allocations (zero page); call once outside stream capture */
 int es_init(void);
 /* The sampling loops.  `step` is the device scalar the plan's ops read; it is set to first_step,
