@@ -9,7 +9,7 @@ CSRC = os.path.join(HERE, 'csrc')
 # ES_BUILD_TAG=_stamp (with ES_BUILD_FLAGS=-DES_STAMP): an instrumented build next to the product library, loaded with ES_LIB_TAG=_stamp
 TAG = os.environ.get('ES_BUILD_TAG', '')
 LIB = os.path.join(HERE, 'libechoscene_hip%s.so' % TAG)
-SOURCES = ['es_runtime.hip', 'es_rows.hip', 'es_vol.hip', 'es_conv_route.hip', 'es_vol32.hip', 'es_keep.hip', 'es_complete.hip', 'es_plms.hip', 'es_layout_ddim.hip', 'es_chamfer.hip', 'es_mc.hip', 'es_mesh_sdf.hip', 'es_shape_metrics.hip', 'es_emd.hip', 'es_layout_metrics.hip', 'es_scene_metrics.hip']
+SOURCES = ['es_runtime.hip', 'es_rows.hip', 'es_vol.hip', 'es_conv_route.hip', 'es_vol32.hip', 'es_update.hip', 'es_boxes.hip', 'es_conv_c1.hip', 'es_complete.hip', 'es_chamfer.hip', 'es_mc.hip', 'es_mesh_sdf.hip', 'es_shape_metrics.hip', 'es_emd.hip', 'es_layout_metrics.hip', 'es_scene_metrics.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function'] + \
     os.environ.get('ES_BUILD_FLAGS', '').split()
 

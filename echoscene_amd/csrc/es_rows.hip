@@ -1,4 +1,4 @@
-// "rows" path: fp32 fused linear over small-M node/triple matrices + the diffusion updates.
+// "rows" path: fp32 fused linear over small-M node/triple matrices (the diffusion updates that consume its slabs: es_update.hip).
 //
 // Roofline note: one layout denoising step streams ~335 MB of fp32 weights for ~6.5 GFLOP --
 // HBM-bound on paper (42 us at 8 TB/s), in practice a chain of ~130 DEPENDENT [32 x K] @ [K x N] products whose cost is
@@ -53,13 +53,8 @@ __device__ __forceinline__ const float* seg_base(const es_seg& s) {
     return p;
 }
 
-__device__ __forceinline__ float load_slabs1(const float* p, int nslab, long slab_stride) {
-    float v = *p;
-    for (int j = 1; j < nslab; ++j) v += p[(long)j * slab_stride];
-    return v;
-}
-// The same sum with the first four loads in flight at once and no control flow: slab j >= nslab re-reads the last slab (same cache
-// line) and is not added.  load_slabs1's run-time loop made every slab of an epilogue operand a dependent round trip IN FRONT of the weight and
+// The fixed-order slab sum of one element (slab 0, + slab 1, ...) with the first four loads in flight at once and no control flow: slab
+// j >= nslab re-reads the last slab (same cache line) and is not added.  A run-time loop made every slab of an epilogue operand a dependent round trip IN FRONT of the weight and
 // staging loads of the slice-0 workgroups (a residual with 4 slabs: four serial L2 / Infinity-Cache round trips before anything else
 // was issued).  Same additions in the same order: the same bits.
 __device__ __forceinline__ void issue_slabs1(float (&r)[4], const float* p, int nslab, long slab_stride) {
@@ -517,69 +512,11 @@ __global__ __launch_bounds__(NTHREAD) void k_linear_rows(const RowsLaunch L) {
 
 #include "es_rows_x.h"
 
-// ONE_BLOCK: the whole state in one workgroup (n <= 4096: one scene) -- the step counter is advanced by the same kernel, after every
-// thread has read it (a launch less per step of the latency-bound layout loop)
-template <bool ONE_BLOCK>
-__global__ void k_ddpm_update(const es_update_args a) {
-#pragma clang fp contract(off)
-    const int st = *a.step;
-    const float* c = a.coef + (long)st * a.coef_stride;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += ONE_BLOCK ? (int)blockDim.x : a.n) {
-        const float x = a.x[i], e = load_slabs1(a.eps + i, a.eps_nslab > 1 ? a.eps_nslab : 1, a.eps_slab_stride);
-        const float nz = a.noise[(long)st * a.noise_stride + i];
-        float x0 = c[0] * x - c[1] * e;
-        if (a.clip_x0) x0 = fminf(fmaxf(x0, -1.0f), 1.0f);          // clip_denoised=True: torch.clamp(x_recon, -1, 1), diffusion_ddpm.py:243-244
-        const float mean = c[2] * x0 + c[3] * x;
-        a.x[i] = mean + c[4] * nz;
-    }
-    if (ONE_BLOCK && a.inc_step) {
-        __syncthreads();
-        if (threadIdx.x == 0) *a.step = st + 1;
-    }
-}
-
-__global__ void k_ddim_update(const es_update_args a) {
-#pragma clang fp contract(off)
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int st = *a.step;
-    if (i < a.n) {
-        const float* c = a.coef + (long)st * a.coef_stride;
-        const float x = a.x[i], e = load_slabs1(a.eps + i, a.eps_nslab > 1 ? a.eps_nslab : 1, a.eps_slab_stride);
-        const float px0 = (x - c[0] * e) / c[1];
-        float xn = c[2] * px0 + c[3] * e;
-        // eta != 0 (samplers/ddim.py:256-260): + sigma_t * randn; c[3] then already is sqrt(1 - a_prev - sigma_t^2), c[4] = sigma_t
-        if (a.noise) xn = xn + c[4] * a.noise[(long)st * a.noise_stride + i];
-        a.x[i] = xn;
-    }
-}
-
-__global__ void k_step_inc(int32_t* step) { *step += 1; }
-
 __global__ void k_row_select(const es_rowsel_args a) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.n) return;
     const float v = a.table[(long)(*a.step) * a.stride + i];
     for (int r = blockIdx.y; r < a.rows; r += gridDim.y) a.out[(long)r * a.out_ld + i] = v;
-}
-
-// Box de-normalisation after the layout loop (helpers/util.py:542-568): [-1,1] -> [min,max] for sizes and
-// translations (in place, stats = {min_lhw[3], max_lhw[3], min_xyz[3], max_xyz[3], min_angle, max_angle}) and
-// (sin, cos) -> arctan2 in degrees-or-radians (scale).
-// ncol = 7: also the angle column (descale_box_params(angle=True), helpers/util.py:553-555: stats[12], stats[13]).
-__global__ void k_box_postprocess(float* boxes, int ld, const float* sincos, float* angle_out, const float* stats,
-                                  int O, float angle_scale, int ncol) {
-#pragma clang fp contract(off)
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= O) return;
-    if (boxes) {
-        for (int c = 0; c < ncol; ++c) {
-            const float lo = stats[c < 3 ? c : c < 6 ? 3 + c : 12], hi = stats[c < 3 ? 3 + c : c < 6 ? 6 + c : 13];
-            float v = boxes[(long)i * ld + c];
-            v = (v + 1.0f) / 2.0f;
-            boxes[(long)i * ld + c] = v * (hi - lo) + lo;
-        }
-    }
-    if (sincos && angle_out) angle_out[i] = atan2f(sincos[2 * i], sincos[2 * i + 1]) * angle_scale;
 }
 
 }  // namespace
@@ -1281,39 +1218,3 @@ extern "C" int es_row_select(const es_rowsel_args* a, es_stream stream) {
     return 0;
 }
 
-extern "C" int es_ddpm_update(const es_update_args* a, es_stream stream) {
-    ES_REQUIRE(a->n > 0 && a->step && a->noise, "es_ddpm_update: bad args");
-    if (a->n <= 4096) {
-        hipLaunchKernelGGL(k_ddpm_update<true>, dim3(1), dim3(256), 0, (hipStream_t)stream, *a);
-    } else {
-        hipLaunchKernelGGL(k_ddpm_update<false>, dim3((a->n + 255) / 256), dim3(256), 0, (hipStream_t)stream, *a);
-        if (a->inc_step) hipLaunchKernelGGL(k_step_inc, dim3(1), dim3(1), 0, (hipStream_t)stream, a->step);
-    }
-    ES_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-extern "C" int es_box_postprocess(float* boxes, int ld, const float* sincos, float* angle_out, const float* stats,
-                                  int O, float angle_scale, es_stream stream) {
-    ES_REQUIRE(O > 0 && (!boxes || (stats && ld >= 6)), "es_box_postprocess: bad args");
-    hipLaunchKernelGGL(k_box_postprocess, dim3((O + 63) / 64), dim3(64), 0, (hipStream_t)stream, boxes, ld, sincos,
-                       angle_out, stats, O, angle_scale, 6);
-    ES_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-extern "C" int es_box_descale(float* boxes, int ld, int ncol, const float* stats, int O, es_stream stream) {
-    ES_REQUIRE(O > 0 && boxes && stats && (ncol == 6 || ncol == 7) && ld >= ncol, "es_box_descale: bad args (ncol=%d, ld=%d)", ncol, ld);
-    hipLaunchKernelGGL(k_box_postprocess, dim3((O + 63) / 64), dim3(64), 0, (hipStream_t)stream, boxes, ld, (const float*)nullptr,
-                       (float*)nullptr, stats, O, 1.0f, ncol);
-    ES_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-extern "C" int es_ddim_update(const es_update_args* a, es_stream stream) {
-    ES_REQUIRE(a->n > 0 && a->step, "es_ddim_update: bad args");
-    hipLaunchKernelGGL(k_ddim_update, dim3((a->n + 255) / 256), dim3(256), 0, (hipStream_t)stream, *a);
-    if (a->inc_step) hipLaunchKernelGGL(k_step_inc, dim3(1), dim3(1), 0, (hipStream_t)stream, a->step);
-    ES_CHECK_HIP(hipGetLastError());
-    return 0;
-}

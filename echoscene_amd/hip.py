@@ -24,8 +24,12 @@ EPI_NONE, EPI_GEGLU = 0, 1
 OP_VQ = 12
 OP_FORK, OP_JOIN, OP_ROWSEL = 13, 14, 15
 OP_CONV_F32, OP_ATTN_F32 = 16, 17          # fp32-operand validation route (csrc/es_vol32.hip)
-OP_DDIM_BLEND, OP_CONV_C1 = 18, 19         # masked-DDIM blend / the VQ-VAE encoder's one-channel conv_in (csrc/es_keep.hip)
-OP_DDPM_KEEP = 21                          # the layout update that also carries the kept rows (csrc/es_keep.hip); 20 stays unassigned
+# the sampler state updates: csrc/es_update.hip.  20, 22 and 26 stay unassigned
+OP_DDIM_BLEND, OP_CONV_C1 = 18, 19         # masked-DDIM blend / the VQ-VAE encoder's one-channel conv_in (csrc/es_conv_c1.hip)
+OP_DDPM_KEEP = 21                          # the layout update that also carries the kept rows
+OP_PLMS, OP_PLMS_FIRST_A, OP_PLMS_FIRST_B = 23, 24, 25     # PLMS sampling of the shape branch
+OP_DDIM_ROWS = 27                          # the strided DDIM update of the layout loop, masked or not (DdpmKeepArgs)
+OP_DDIM_BLEND_VOX = 28                     # masked-DDIM blend with a mask per latent voxel: shape completion
 
 
 class Seg(C.Structure):
@@ -125,12 +129,6 @@ class VQArgs(C.Structure):
 class BlendArgs(C.Structure):
     _fields_ = [('x', C.c_void_p), ('x0', C.c_void_p), ('mask', C.c_void_p), ('noise', C.c_void_p), ('noise_stride', C.c_int32),
                 ('tab', C.c_void_p), ('step', C.c_void_p), ('O', C.c_int32), ('n', C.c_int32)]
-
-OP_PLMS, OP_PLMS_FIRST_A, OP_PLMS_FIRST_B = 23, 24, 25     # PLMS sampling of the shape branch (csrc/es_plms.hip); 22 stays unassigned
-OP_DDIM_ROWS = 27                          # the strided DDIM update of the layout loop, masked or not (csrc/es_layout_ddim.hip; DdpmKeepArgs); 26 stays unassigned
-
-
-OP_DDIM_BLEND_VOX = 28                     # masked-DDIM blend with a mask per latent voxel: shape completion (csrc/es_complete.hip)
 
 
 class BlendVoxArgs(C.Structure):

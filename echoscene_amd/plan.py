@@ -535,22 +535,24 @@ class Builder:
         self.ops[i].u.linear.fuse_next = 1
         return n_group + 1
 
+    def _update_prefix(self, a, x, eps, coef, step, noise, noise_stride, inc_step, clip_x0):
+        """the members UpdateArgs and DdpmKeepArgs share.  eps: tensor or (slab) View; noise: View or None"""
+        if isinstance(eps, View):
+            assert eps.ld == eps.width and eps.col == 0
+            a.eps, a.eps_nslab, a.eps_slab_stride = eps.ptr, eps.nslab, eps.slab_stride
+            self.keep.append(eps.t)
+        else:
+            a.eps = eps.data_ptr()
+        a.x, a.n = x.data_ptr(), x.numel()
+        a.noise, a.noise_stride = (noise.ptr if noise is not None else None), noise_stride
+        a.coef, a.coef_stride = coef.data_ptr(), coef.shape[1]
+        a.step, a.inc_step = step.data_ptr(), 1 if inc_step else 0
+        a.clip_x0 = 1 if clip_x0 else 0
+
     def update(self, kind, x, eps, coef, step, noise=None, noise_stride=0, inc_step=True, clip_x0=False):
         """eps: tensor or (slab) View"""
         a = UpdateArgs()
-        if isinstance(eps, View):
-            assert eps.ld == eps.width and eps.col == 0
-            a.x, a.eps, a.eps_nslab, a.eps_slab_stride = x.data_ptr(), eps.ptr, eps.nslab, eps.slab_stride
-            self.keep.append(eps.t)
-        else:
-            a.x, a.eps = x.data_ptr(), eps.data_ptr()
-        a.noise = noise.ptr if noise is not None else None
-        a.noise_stride = noise_stride
-        a.coef, a.coef_stride = coef.data_ptr(), coef.shape[1]
-        a.step = step.data_ptr()
-        a.n = x.numel()
-        a.inc_step = 1 if inc_step else 0
-        a.clip_x0 = 1 if clip_x0 else 0
+        self._update_prefix(a, x, eps, coef, step, noise, noise_stride, inc_step, clip_x0)
         op = Op()
         op.kind, op.lane = kind, 0
         op.u.update = a
@@ -561,18 +563,7 @@ class Builder:
         mask is 0, the next iteration's q_sample of ``x0`` (or ``x0`` itself after the last one) on the others.  x, x0 [O, row];
         mask [O]; keep_noise [T, O * row]; tab [T, 2] (LayoutSchedule.keep_tab)"""
         a = DdpmKeepArgs()
-        if isinstance(eps, View):
-            assert eps.ld == eps.width and eps.col == 0
-            a.x, a.eps, a.eps_nslab, a.eps_slab_stride = x.data_ptr(), eps.ptr, eps.nslab, eps.slab_stride
-            self.keep.append(eps.t)
-        else:
-            a.x, a.eps = x.data_ptr(), eps.data_ptr()
-        a.noise, a.noise_stride = noise.ptr, noise_stride
-        a.coef, a.coef_stride = coef.data_ptr(), coef.shape[1]
-        a.step = step.data_ptr()
-        a.n = x.numel()
-        a.inc_step = 1 if inc_step else 0
-        a.clip_x0 = 1 if clip_x0 else 0
+        self._update_prefix(a, x, eps, coef, step, noise, noise_stride, inc_step, clip_x0)
         a.x0, a.mask, a.keep_noise = x0.data_ptr(), mask.data_ptr(), keep_noise.data_ptr()
         a.keep_noise_stride = keep_noise.shape[1]
         a.tab, a.n_tab = tab.data_ptr(), tab.shape[0]
@@ -590,18 +581,7 @@ class Builder:
         ``noise`` (a View of the per-iteration draws) only when eta != 0; x0 / mask / keep_noise [S, O * row] / tab [S, 2] together or
         not at all"""
         a = DdpmKeepArgs()
-        if isinstance(eps, View):
-            assert eps.ld == eps.width and eps.col == 0
-            a.x, a.eps, a.eps_nslab, a.eps_slab_stride = x.data_ptr(), eps.ptr, eps.nslab, eps.slab_stride
-            self.keep.append(eps.t)
-        else:
-            a.x, a.eps = x.data_ptr(), eps.data_ptr()
-        a.noise, a.noise_stride = (noise.ptr if noise is not None else None), noise_stride
-        a.coef, a.coef_stride = coef.data_ptr(), coef.shape[1]
-        a.step = step.data_ptr()
-        a.n = x.numel()
-        a.inc_step = 1 if inc_step else 0
-        a.clip_x0 = 0
+        self._update_prefix(a, x, eps, coef, step, noise, noise_stride, inc_step, False)
         a.n_tab = coef.shape[0]
         a.row = x.numel() // x.shape[0]
         given = [t is not None for t in (x0, mask, keep_noise, tab)]

@@ -49,7 +49,7 @@ def layout_betas(schedule_type, beta_start, beta_end, time_num):
 
 class LayoutSchedule:
     """Per-iteration coefficients of the ancestral DDPM loop, iteration i <-> t = T-1-i: five numbers per step,
-    ``x0 = c0 * x - c1 * out;  mean = c2 * x0 + c3 * x;  x' = mean + c4 * noise`` (k_ddpm_update, fp contraction off).
+    ``x0 = c0 * x - c1 * out;  mean = c2 * x0 + c3 * x;  x' = mean + c4 * noise`` (ddpm_step, csrc/es_update.hip: fp contraction off).
 
     ``model_mean_type`` (p_mean_variance, diffusion_ddpm.py:239-257): 'eps' -> c0, c1 = sqrt(1 / ac), sqrt(1 / ac - 1);
     'x0' (the network predicts x_0 itself) -> c0, c1 = 0, -1: ``0 * x - (-1 * out)`` is ``out`` bit for bit, so the update kernel is

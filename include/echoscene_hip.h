@@ -231,7 +231,7 @@ typedef struct es_blend_args {
     int32_t O, n;           /* objects, floats per object (n % 4 == 0)                          */
 } es_blend_args;
 int es_ddim_blend(const es_blend_args* args, es_stream stream);
-/* Shape completion (csrc/es_complete.hip): the same blend with a mask per latent VOXEL, shared by the C channels -- the z_mask
+/* Shape completion: the same blend with a mask per latent VOXEL, shared by the C channels -- the z_mask
  * [B, 1, zH, zW, zD] of get_partial_shape (diffusion_shape/diff_utils/demo_util.py:229-252) that shape_comp hands to the sampler
  * (diffusion_shape/sdfusion_model.py:400-446):
  *     x[o, c, v] = mask[o, v] != 0 ? tab[2*step] * x0[o, c, v] + tab[2*step + 1] * noise[step][o, c, v] : x[o, c, v]

@@ -59,7 +59,9 @@ def _ref_update(x, eps, nz, c, clip, mask, x0, tab, kn, st):
 def test_ddpm_update_keep_kernel_vs_torch_bitwise(dev, O):
     """es_ddpm_update_keep through the C ABI at n = 8, 24, 4096 (the last size of the one-workgroup path) and 4104 (the first of the
     multi-workgroup path): masks none / all / first-and-last kept, steps 0 / middle / n_tab - 1 (with one NaN row behind tab and
-    keep_noise, which must not be read), eps as 1 and 2 slabs, clip_x0 0 / 1, inc_step 0 / 1 with the counter checked."""
+    keep_noise, which must not be read), eps as 1 and 2 slabs, clip_x0 0 / 1, inc_step 0 / 1 with the counter checked.  A fourth
+    mask case, 'plain', is es_ddpm_update with UpdateArgs -- no x0 / tab / keep_noise at all -- against the reference with a zero
+    mask: it runs the same kernel with mask == NULL."""
     from echoscene_amd import hip
     from echoscene_amd.schedules import LayoutSchedule
     L = hip.lib()
@@ -84,10 +86,15 @@ def test_ddpm_update_keep_kernel_vs_torch_bitwise(dev, O):
     a.eps_slab_stride, a.noise_stride, a.coef_stride, a.n = n, n, 5, n
     a.x0, a.keep_noise, a.tab = x0_d.data_ptr(), kn_d.data_ptr(), tab_d.data_ptr()
     a.keep_noise_stride, a.n_tab, a.row = n, N_TAB, row
+    u = hip.UpdateArgs()
+    u.x, u.eps, u.noise, u.coef, u.step = a.x, a.eps, a.noise, a.coef, a.step
+    u.eps_slab_stride, u.noise_stride, u.coef_stride, u.n = n, n, 5, n
+    masks['plain'] = torch.zeros(O)
     checked = 0
     for mname, mask in masks.items():
         mask_d = d(mask)
         a.mask = mask_d.data_ptr()
+        plain = mname == 'plain'
         for st in (0, 7, N_TAB - 1):
             for nslab in (1, 2):
                 for clip in (0, 1):
@@ -95,7 +102,11 @@ def test_ddpm_update_keep_kernel_vs_torch_bitwise(dev, O):
                         x_d.copy_(x_in)
                         step_d.fill_(st)
                         a.eps_nslab, a.clip_x0, a.inc_step = nslab, clip, inc
-                        hip.check(L.es_ddpm_update_keep(C.byref(a), hip.current_stream()), 'es_ddpm_update_keep')
+                        u.eps_nslab, u.clip_x0, u.inc_step = nslab, clip, inc
+                        if plain:
+                            hip.check(L.es_ddpm_update(C.byref(u), hip.current_stream()), 'es_ddpm_update')
+                        else:
+                            hip.check(L.es_ddpm_update_keep(C.byref(a), hip.current_stream()), 'es_ddpm_update_keep')
                         got, stc = x_d.cpu(), int(step_d.item())
                         ref = _ref_update(x_in, eps[:nslab], noise[st], coef[st], clip, mask, x0, tab, kn, st)
                         tag = 'O=%d mask=%s step=%d slabs=%d clip=%d inc=%d' % (O, mname, st, nslab, clip, inc)
@@ -105,7 +116,7 @@ def test_ddpm_update_keep_kernel_vs_torch_bitwise(dev, O):
                         if st == N_TAB - 1:
                             assert torch.equal(got[mask.bool()], x0[mask.bool()]), tag
                         checked += 1
-    assert checked == 72
+    assert checked == 96
     # the two halves really differ on these inputs (a kernel that ignored the mask would not pass)
     r0 = _ref_update(x_in, eps[:1], noise[0], coef[0], 0, masks['none'], x0, tab, kn, 0)
     r1 = _ref_update(x_in, eps[:1], noise[0], coef[0], 0, masks['all'], x0, tab, kn, 0)

@@ -213,7 +213,7 @@ def test_sampler_variants_schedules_x0_prediction_fixedlarge():
         x = orc.layout_sample_loop(sd, g['obj_embed'], g['triples'], noise, time_num=100, clip_denoised=clip, **kw)
         _close(x, g['x_final_' + tag], 1e-4)
         assert (x - plain).abs().max() > 1e-3
-        # the product's table: x0 = c0 x - c1 out; mean = c2 x0 + c3 x; x' = mean + c4 noise (k_ddpm_update, no contraction)
+        # the product's table: x0 = c0 x - c1 out; mean = c2 x0 + c3 x; x' = mean + c4 noise (ddpm_step of es_update.hip, no contraction)
         sch = LayoutSchedule(100, 1e-4, 0.02, **kw)
         tab = orc.ddpm_tables(1e-4, 0.02, 100, kw['schedule_type'])
         rs = np.random.RandomState(5)
