@@ -76,7 +76,7 @@ struct ConvRoute {
 // ranks -- or a process that saves a model file and one that replays it -- with different environments silently disagreed.  Now they
 // are process-wide options with constant defaults that ONLY an explicit es_vol_set_option() call changes (tests and A/B tools);
 // es_model_save records them in the file and es_model_load refuses a file written under other values.  conv_route() is the only
-// reader of the conv_* options (gn_rg: es_groupnorm_vol).  The three env_* members are NOT options: environment switches -- ES_CONV_A3,
+// reader of the conv_* options (gn_rg: gn_route(), the rule of es_groupnorm_vol).  The three env_* members are NOT options: environment switches -- ES_CONV_A3,
 // ES_CONV_LINWS, ES_CONV_N16 -- that move a launch between kernels with the same K order and the same bits, read
 // once per process and recorded nowhere; the A/B switches whose variant lost (ES_CONV_NS, ES_CONV_GB, ES_LIN_RING, ES_LIN_NCB_MAX)
 // went with the kernel variants only they reached.
@@ -99,7 +99,7 @@ struct RouteOptions {
     int env_n16 = 1;               // ES_CONV_N16 = 0: no k_conv_n16
 };
 // the process-wide instance: es_vol_set_option() writes it, es_vol_options() prints it, the extern "C" queries, es_conv_mfma_f16 and
-// es_groupnorm_vol (gn_rg) read it
+// es_groupnorm_vol (gn_route(): gn_rg) read it
 const RouteOptions& es_route_options();
 
 // The pure function: 0 and the route in *r, or 2 with es_set_error() on arguments the conv refuses
@@ -117,3 +117,38 @@ inline int gn_voxel_tile(long Oh, int V) {
     while (vt > 8 && Oh * ((V + vt - 1) / vt) < 512) vt >>= 1;
     return vt;
 }
+
+// log2 of TX, the lanes k_gn_apply lays across the 8-channel chunks of a voxel: the chunk count rounded up to a power of two, at most
+// 32 (constexpr: the kernel itself evaluates this rule, gn_route() reports it)
+constexpr int gn_apply_log2_tx(int c8n) {
+    int lt = 5;
+    while (lt > 0 && (1 << (lt - 1)) >= c8n) --lt;
+    return lt;
+}
+
+// ---- The route of one es_groupnorm_vol launch: gn_route() DECIDES (tiles, statistics source, whether k_gn_finalize runs, where the
+// final statistics go, voxels per apply block, every grid), es_groupnorm_vol (es_vol.hip) LAUNCHES what it names and decides nothing,
+// es_groupnorm_route_of reads it for tests.
+enum class GnStats { pass = ES_GN_STATS_PASS, part_in = ES_GN_STATS_PART_IN, rowgroup = ES_GN_STATS_ROWGROUP };
+struct GnRoute {
+    int vt, ntiles;
+    GnStats src;
+    bool finalize;             // k_gn_finalize (long tile lists: the statistics reduced once per object, not in every apply block)
+    long fin_off;              // floats from es_gn_args.stats to the final statistics k_gn_apply reads; -1: it reduces the partials itself
+    int vpb, TX;
+    unsigned partial_gx, partial_gy, fin_gx, fin_gy, apply_gx, apply_gy;      // 0, 0: that launch does not run
+};
+// 0 and the route in *r, or 2 with es_set_error() on arguments the GroupNorm refuses
+int gn_route(const es_gn_args& a, const RouteOptions& o, GnRoute* r);
+
+// ---- The instantiation of one es_attention_f16 / es_attention_f32 launch (es_attention_route_of reads it for tests)
+enum class AttnKernel { h32_1, h32_2, h64_1, h64_2, h96_1, h96_2, h256_1, f32m_64, f32m_96, f32_64, f32_96 };
+extern const char* const kAttnKernelName[(int)AttnKernel::f32_96 + 1];
+struct AttnRoute {
+    AttnKernel kernel;
+    int DP, rows;              // padded head dimension, query rows per workgroup
+    unsigned gx, gy;
+    int block;                 // threads per workgroup
+    size_t lds;                // dynamic LDS bytes
+};
+int attn_route(const es_attn_args& a, bool fp32, AttnRoute* r);

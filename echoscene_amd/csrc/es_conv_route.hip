@@ -535,3 +535,102 @@ extern "C" int es_conv_fold_balanced(const es_conv_args* a) {
     es_conv_route_info i;
     return es_conv_route_of(a, &i) == 0 ? i.fold_bal : -1;
 }
+
+// ---- es_groupnorm_vol: the launch decisions.  Voxel-tile sizes by workgroup count: small problems (few objects per GPU when sharded)
+// get smaller tiles; tile sizes from the whole problem when this launch is a shard (O_hint > O), from the reference shard when
+// O_hint < 0. ---------------------------------------------------------------------------------------------------------------------
+int gn_route(const es_gn_args& a, const RouteOptions& o, GnRoute* r) {
+    const int C = a.C1 + a.C2;
+    ES_REQUIRE(a.groups > 0 && C > 0 && C % a.groups == 0 && C <= 2048 && a.groups <= 64, "es_groupnorm_vol: C=%d groups=%d", C, a.groups);
+    ES_REQUIRE(a.C1 % 8 == 0 && a.C2 % 8 == 0, "es_groupnorm_vol: channel counts must be multiples of 8 (%d,%d)", a.C1, a.C2);
+    ES_REQUIRE(a.O > 0 && a.V > 0, "es_groupnorm_vol: O=%d V=%d", a.O, a.V);
+    ES_REQUIRE(a.stats != nullptr, "es_groupnorm_vol: stats scratch missing");
+    const long Oh = a.O_hint < 0 ? -(long)a.O_hint : (long)(a.O_hint > a.O ? a.O_hint : a.O);
+    r->vt = gn_voxel_tile(Oh, a.V);
+    r->ntiles = (a.V + r->vt - 1) / r->vt;
+    const bool from_rg = a.stats1 && (!a.x2 || a.stats2) && a.V % 64 == 0 && (a.x1_is_f16 || o.gn_rg != 0);
+    ES_REQUIRE(!a.x1_is_f16 || (from_rg && !a.x2 && !a.raw_f16),
+               "es_groupnorm_vol: an f16 source needs the producer's row-group sums (stats1), one source, no raw copy");
+    ES_REQUIRE(!a.part_in || (!from_rg && !a.x2), "es_groupnorm_vol: part_in needs one source and no row-group sums");
+    r->src = from_rg ? GnStats::rowgroup : a.part_in ? GnStats::part_in : GnStats::pass;
+    r->partial_gx = r->partial_gy = r->fin_gx = r->fin_gy = 0;
+    if (r->src == GnStats::pass) { r->partial_gx = (unsigned)r->ntiles; r->partial_gy = (unsigned)a.O; }
+    int vpb = 32;
+    while (vpb > 8 && (long)a.O * ((a.V + vpb - 1) / vpb) < 512) vpb >>= 1;
+    while (vpb < 1024 && (long)a.O * ((a.V + vpb - 1) / vpb) > 16384) vpb <<= 1;     // (64^3 volumes: fewer, larger blocks)
+    r->vpb = vpb;
+    // long tile lists (VQ-VAE decoder at 32^3 / 64^3): the statistics are reduced ONCE per object; the final [O][groups][2] floats
+    // sit behind the partials in the caller's scratch (es_gn_args.stats)
+    r->finalize = !from_rg && r->ntiles > 128;
+    r->fin_off = -1;
+    if (from_rg) {                 // statistics from the producers' row-group sums: no pass over x1 / x2
+        r->fin_off = 0;
+    } else if (r->finalize) {
+        // (with part_in the partials live in the PRODUCER's buffer, which has no room behind them: the final statistics go to the
+        //  front of the caller's own scratch then.  Until round 6 they were written behind part_in -- 256 bytes past the end of a
+        //  buffer that ends on a page boundary was a GPU memory fault at one object per GPU, 16^3 level)
+        r->fin_off = a.part_in ? 0 : (long)a.O * r->ntiles * a.groups * 2;
+    }
+    if (r->fin_off >= 0) { r->fin_gx = (unsigned)a.groups; r->fin_gy = (unsigned)a.O; }
+    r->TX = 1 << gn_apply_log2_tx(C >> 3);
+    r->apply_gx = (unsigned)((a.V + vpb - 1) / vpb);
+    r->apply_gy = (unsigned)a.O;
+    return 0;
+}
+
+extern "C" int es_groupnorm_route_of(const es_gn_args* a, es_gn_route_info* out) {
+    GnRoute r;
+    if (gn_route(*a, es_route_options(), &r) != 0) return -1;
+    *out = es_gn_route_info{r.vt, r.ntiles, (int32_t)r.src, (int32_t)r.finalize, (int32_t)r.fin_off, r.vpb, r.TX,
+                            r.partial_gx, r.partial_gy, r.fin_gx, r.fin_gy, r.apply_gx, r.apply_gy};
+    return 0;
+}
+
+// ---- es_attention_f16 / es_attention_f32: the instantiation by head dimension and sequence length ----------------------------------
+const char* const kAttnKernelName[] = {
+    "attention_32_4_1", "attention_32_4_2", "attention_64_4_1", "attention_64_4_2", "attention_96_4_1", "attention_96_4_2", "attention_256_4_1",
+    "attention_f32m_64", "attention_f32m_96", "attention_f32_64", "attention_f32_96"
+};
+
+int attn_route(const es_attn_args& a, bool fp32, AttnRoute* r) {
+    ES_REQUIRE(a.B > 0 && a.Ntok > 0 && a.heads > 0, "es_attention: B=%d Ntok=%d heads=%d", a.B, a.Ntok, a.heads);
+    r->lds = 0;
+    if (fp32) {
+        ES_REQUIRE(a.dhead > 0 && a.dhead <= 96, "es_attention_f32: dhead=%d (<= 96)", a.dhead);
+        r->rows = 64;
+        r->DP = a.dhead <= 64 ? 64 : 96;
+        if (a.dhead % 4 == 0) {
+            // round 6: the matrix-instruction kernel (dhead a multiple of 4: the K / V tiles are staged in 16-byte quads): K and V tiles
+            // of 64 keys x (DP + 4) floats, and 4 waves x 16 rows x 68 floats of probabilities
+            r->kernel = a.dhead <= 64 ? AttnKernel::f32m_64 : AttnKernel::f32m_96;
+            r->block = 256;
+            r->lds = (size_t)(2 * 64 * (r->DP + 4) + 4 * 16 * 68) * 4;
+        } else {
+            r->kernel = a.dhead <= 64 ? AttnKernel::f32_64 : AttnKernel::f32_96;
+            r->block = 64;
+        }
+    } else {
+        ES_REQUIRE(a.dhead % 4 == 0 && a.dhead <= 256 && a.dhead > 0, "es_attention_f16: dhead=%d (multiple of 4, <= 256)", a.dhead);
+        ES_REQUIRE(a.scale > 0.f, "es_attention_f16: scale=%g must be positive (the row maximum is taken over the raw scores)", (double)a.scale);
+        const bool big = a.Ntok >= 512 && a.dhead <= 96;       // 128 query rows per workgroup (4 waves x 2 row tiles), else 64 (4 x 1)
+        r->rows = big ? 128 : 64;
+        r->block = 256;
+        if (a.dhead <= 32) { r->DP = 32; r->kernel = big ? AttnKernel::h32_2 : AttnKernel::h32_1; }
+        else if (a.dhead <= 64) { r->DP = 64; r->kernel = big ? AttnKernel::h64_2 : AttnKernel::h64_1; }
+        else if (a.dhead <= 96) { r->DP = 96; r->kernel = big ? AttnKernel::h96_2 : AttnKernel::h96_1; }
+        else { r->DP = 256; r->kernel = AttnKernel::h256_1; }
+    }
+    r->gx = (unsigned)((a.Ntok + r->rows - 1) / r->rows);
+    r->gy = (unsigned)(a.B * a.heads);
+    return 0;
+}
+
+extern "C" int es_attention_route_of(const es_attn_args* a, int fp32, es_attn_route_info* out) {
+    AttnRoute r;
+    if (attn_route(*a, fp32 != 0, &r) != 0) return -1;
+    es_attn_route_info i{};
+    snprintf(i.kernel, sizeof(i.kernel), "%s", kAttnKernelName[(int)r.kernel]);
+    i.DP = r.DP; i.rows = r.rows; i.grid_x = r.gx; i.grid_y = r.gy; i.block = r.block; i.lds = (int32_t)r.lds;
+    *out = i;
+    return 0;
+}

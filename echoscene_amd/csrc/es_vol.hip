@@ -170,8 +170,7 @@ __global__ __launch_bounds__(256) void k_gn_apply(const es_gn_args a, const floa
     }
     __syncthreads();
     const int c8n = C >> 3;
-    int lt = 5;                                          // log2(TX)
-    while (lt > 0 && (1 << (lt - 1)) >= c8n) --lt;
+    const int lt = gn_apply_log2_tx(c8n);                // log2(TX): the rule gn_route() reports (es_conv_route.h)
     const int TX = 1 << lt, TY = 256 >> lt;
     const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x >> lt;
     const int v0 = blockIdx.x * vox_per_block;
@@ -3105,40 +3104,16 @@ extern "C" int es_conv_mfma_f16(const es_conv_args* a, es_stream stream) {
 }
 
 extern "C" int es_groupnorm_vol(const es_gn_args* a, es_stream stream) {
-    const int C = a->C1 + a->C2;
-    ES_REQUIRE(C % a->groups == 0 && C <= 2048 && a->groups <= 64, "es_groupnorm_vol: C=%d groups=%d", C, a->groups);
-    ES_REQUIRE(a->C1 % 8 == 0 && a->C2 % 8 == 0, "es_groupnorm_vol: channel counts must be multiples of 8 (%d,%d)", a->C1, a->C2);
-    ES_REQUIRE(a->stats != nullptr, "es_groupnorm_vol: stats scratch missing");
-    // voxel-tile sizes by workgroup count: small problems (few objects per GPU when sharded) get smaller tiles
-    // tile sizes from the whole problem when this launch is a shard (O_hint > O), from the reference shard when O_hint < 0
-    const long Oh = a->O_hint < 0 ? -(long)a->O_hint : (long)(a->O_hint > a->O ? a->O_hint : a->O);
-    const int vt = gn_voxel_tile(Oh, a->V);
-    const int ntiles = (a->V + vt - 1) / vt;
+    GnRoute r;                   // every number below is gn_route()'s (es_conv_route.hip): this function launches what it names
+    if (int err = gn_route(*a, es_route_options(), &r)) return err;
+    hipStream_t st = (hipStream_t)stream;
     float* part = a->stats;      // caller-provided scratch of O*ceil(V/8)*groups*2 floats
-    const bool from_rg = a->stats1 && (!a->x2 || a->stats2) && a->V % 64 == 0 && (a->x1_is_f16 || es_route_options().gn_rg != 0);
-    ES_REQUIRE(!a->x1_is_f16 || (from_rg && !a->x2 && !a->raw_f16),
-               "es_groupnorm_vol: an f16 source needs the producer's row-group sums (stats1), one source, no raw copy");
-    ES_REQUIRE(!a->part_in || (!from_rg && !a->x2), "es_groupnorm_vol: part_in needs one source and no row-group sums");
-    if (a->part_in) part = (float*)a->part_in;
-    else if (!from_rg) hipLaunchKernelGGL(k_gn_partial, dim3(ntiles, a->O), dim3(256), 0, (hipStream_t)stream, *a, part, vt);
-    int vpb = 32;
-    while (vpb > 8 && (long)a->O * ((a->V + vpb - 1) / vpb) < 512) vpb >>= 1;
-    while (vpb < 1024 && (long)a->O * ((a->V + vpb - 1) / vpb) > 16384) vpb <<= 1;     // (64^3 volumes: fewer, larger blocks)
-    // long tile lists (VQ-VAE decoder at 32^3 / 64^3): the statistics are reduced ONCE per object; the final [O][groups][2] floats
-    // sit behind the partials in the caller's scratch (es_gn_args.stats)
-    const float* fin = nullptr;
-    if (from_rg) {                 // statistics from the producers' row-group sums: no pass over x1 / x2
-        hipLaunchKernelGGL(k_gn_finalize_rg, dim3(a->groups, a->O), dim3(256), 0, (hipStream_t)stream, *a, part);
-        fin = part;
-    } else if (ntiles > 128) {
-        // (with part_in the partials live in the PRODUCER's buffer, which has no room behind them: the final statistics go to the
-        //  front of the caller's own scratch then.  Until round 6 they were written behind part_in -- 256 bytes past the end of a
-        //  buffer that ends on a page boundary was a GPU memory fault at one object per GPU, 16^3 level)
-        float* f = a->part_in ? a->stats : part + (size_t)a->O * ntiles * a->groups * 2;
-        hipLaunchKernelGGL(k_gn_finalize, dim3(a->groups, a->O), dim3(256), 0, (hipStream_t)stream, *a, part, ntiles, f);
-        fin = f;
-    }
-    hipLaunchKernelGGL(k_gn_apply, dim3((a->V + vpb - 1) / vpb, a->O), dim3(256), 0, (hipStream_t)stream, *a, part, ntiles, vpb, fin);
+    if (r.src == GnStats::part_in) part = (float*)a->part_in;
+    else if (r.src == GnStats::pass) hipLaunchKernelGGL(k_gn_partial, dim3(r.partial_gx, r.partial_gy), dim3(256), 0, st, *a, part, r.vt);
+    float* fin = r.fin_off >= 0 ? a->stats + r.fin_off : nullptr;
+    if (r.src == GnStats::rowgroup) hipLaunchKernelGGL(k_gn_finalize_rg, dim3(r.fin_gx, r.fin_gy), dim3(256), 0, st, *a, fin);
+    else if (r.finalize) hipLaunchKernelGGL(k_gn_finalize, dim3(r.fin_gx, r.fin_gy), dim3(256), 0, st, *a, part, r.ntiles, fin);
+    hipLaunchKernelGGL(k_gn_apply, dim3(r.apply_gx, r.apply_gy), dim3(256), 0, st, *a, part, r.ntiles, r.vpb, fin);
     ES_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -3154,16 +3129,20 @@ extern "C" int es_layernorm_tokens(const es_ln_args* a, es_stream stream) {
 }
 
 extern "C" int es_attention_f16(const es_attn_args* a, es_stream stream) {
-    ES_REQUIRE(a->dhead % 4 == 0 && a->dhead <= 256 && a->dhead > 0, "es_attention_f16: dhead=%d (multiple of 4, <= 256)", a->dhead);
-    ES_REQUIRE(a->scale > 0.f, "es_attention_f16: scale=%g must be positive (the row maximum is taken over the raw scores)", (double)a->scale);
-    const bool big = a->Ntok >= 512 && a->dhead <= 96;       // 128 query rows per workgroup (4 waves x 2 row tiles), else 64 (4 x 1)
-    const int rows = big ? 128 : 64;
-    dim3 grid((a->Ntok + rows - 1) / rows, a->B * a->heads);
+    AttnRoute r;                 // attn_route() (es_conv_route.hip) chooses the instantiation and the grid
+    if (int err = attn_route(*a, false, &r)) return err;
+    const dim3 grid(r.gx, r.gy), block(r.block);
     hipStream_t st = (hipStream_t)stream;
-    if (a->dhead <= 32) { if (big) hipLaunchKernelGGL((k_attention<32, 4, 2>), grid, dim3(256), 0, st, *a); else hipLaunchKernelGGL((k_attention<32, 4, 1>), grid, dim3(256), 0, st, *a); }
-    else if (a->dhead <= 64) { if (big) hipLaunchKernelGGL((k_attention<64, 4, 2>), grid, dim3(256), 0, st, *a); else hipLaunchKernelGGL((k_attention<64, 4, 1>), grid, dim3(256), 0, st, *a); }
-    else if (a->dhead <= 96) { if (big) hipLaunchKernelGGL((k_attention<96, 4, 2>), grid, dim3(256), 0, st, *a); else hipLaunchKernelGGL((k_attention<96, 4, 1>), grid, dim3(256), 0, st, *a); }
-    else hipLaunchKernelGGL((k_attention<256, 4, 1>), grid, dim3(256), 0, st, *a);
+    switch (r.kernel) {
+        case AttnKernel::h32_1: hipLaunchKernelGGL((k_attention<32, 4, 1>), grid, block, r.lds, st, *a); break;
+        case AttnKernel::h32_2: hipLaunchKernelGGL((k_attention<32, 4, 2>), grid, block, r.lds, st, *a); break;
+        case AttnKernel::h64_1: hipLaunchKernelGGL((k_attention<64, 4, 1>), grid, block, r.lds, st, *a); break;
+        case AttnKernel::h64_2: hipLaunchKernelGGL((k_attention<64, 4, 2>), grid, block, r.lds, st, *a); break;
+        case AttnKernel::h96_1: hipLaunchKernelGGL((k_attention<96, 4, 1>), grid, block, r.lds, st, *a); break;
+        case AttnKernel::h96_2: hipLaunchKernelGGL((k_attention<96, 4, 2>), grid, block, r.lds, st, *a); break;
+        case AttnKernel::h256_1: hipLaunchKernelGGL((k_attention<256, 4, 1>), grid, block, r.lds, st, *a); break;
+        default: ES_REQUIRE(false, "es_attention_f16: no kernel for route %d", (int)r.kernel);
+    }
     ES_CHECK_HIP(hipGetLastError());
     return 0;
 }

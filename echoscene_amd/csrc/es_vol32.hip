@@ -7,6 +7,7 @@
 // LDS-tiled implicit-GEMM kernel for every conv / linear shape, a flash-style fp32 attention, and fp32-output variants of the
 // normalisation kernels (es_vol.hip, `*_is_f32` flags).  Same op list, same fusion structure, same epilogue order as the fp16 route.
 #include "es_common.h"
+#include "es_conv_route.h"
 #include <mutex>
 #include <algorithm>
 
@@ -325,24 +326,27 @@ extern "C" int es_conv_f32(const es_conv_args* a, es_stream stream) {
 }
 
 extern "C" int es_attention_f32(const es_attn_args* a, es_stream stream) {
-    ES_REQUIRE(a->dhead > 0 && a->dhead <= 96, "es_attention_f32: dhead=%d (<= 96)", a->dhead);
-    dim3 grid((a->Ntok + 63) / 64, a->B * a->heads);
+    AttnRoute r;                 // attn_route() (es_conv_route.hip) chooses the kernel, the grid and the dynamic LDS
+    if (int err = attn_route(*a, true, &r)) return err;
+    const dim3 grid(r.gx, r.gy), block(r.block);
     hipStream_t st = (hipStream_t)stream;
-    if (a->dhead % 4 == 0) {
-        // round 6: the matrix-instruction kernel (dhead a multiple of 4: the K / V tiles are staged in 16-byte quads)
+    if (r.kernel == AttnKernel::f32m_96) {
+        // the matrix-instruction kernel at DP = 96 needs more dynamic LDS than the default limit (one size per instantiation)
         static std::once_flag once;
         static hipError_t attr_err = hipSuccess;
-        std::call_once(once, [] {
-            attr_err = hipFuncSetAttribute((const void*)k_attention_f32m<96>, hipFuncAttributeMaxDynamicSharedMemorySize, (2 * 64 * 100 + 4 * 16 * 68) * 4);
+        const int lds96 = (int)r.lds;
+        std::call_once(once, [lds96] {
+            attr_err = hipFuncSetAttribute((const void*)k_attention_f32m<96>, hipFuncAttributeMaxDynamicSharedMemorySize, lds96);
         });
         ES_REQUIRE(attr_err == hipSuccess, "es_attention_f32: hipFuncSetAttribute failed: %s", hipGetErrorString(attr_err));
-        if (a->dhead <= 64) hipLaunchKernelGGL((k_attention_f32m<64>), grid, dim3(256), (2 * 64 * 68 + 4 * 16 * 68) * 4, st, *a);
-        else hipLaunchKernelGGL((k_attention_f32m<96>), grid, dim3(256), (2 * 64 * 100 + 4 * 16 * 68) * 4, st, *a);
-        ES_CHECK_HIP(hipGetLastError());
-        return 0;
     }
-    if (a->dhead <= 64) hipLaunchKernelGGL((k_attention_f32<64>), grid, dim3(64), 0, st, *a);
-    else hipLaunchKernelGGL((k_attention_f32<96>), grid, dim3(64), 0, st, *a);
+    switch (r.kernel) {
+        case AttnKernel::f32m_64: hipLaunchKernelGGL((k_attention_f32m<64>), grid, block, r.lds, st, *a); break;
+        case AttnKernel::f32m_96: hipLaunchKernelGGL((k_attention_f32m<96>), grid, block, r.lds, st, *a); break;
+        case AttnKernel::f32_64: hipLaunchKernelGGL((k_attention_f32<64>), grid, block, r.lds, st, *a); break;
+        case AttnKernel::f32_96: hipLaunchKernelGGL((k_attention_f32<96>), grid, block, r.lds, st, *a); break;
+        default: ES_REQUIRE(false, "es_attention_f32: no kernel for route %d", (int)r.kernel);
+    }
     ES_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -97,6 +97,21 @@ class AttnArgs(C.Structure):
                 ('dhead', C.c_int32), ('scale', C.c_float), ('out_f16', C.c_void_p)]
 
 
+class GNRouteInfo(C.Structure):
+    """es_gn_route_info: every launch decision of es_groupnorm_vol (es_groupnorm_route_of; host-only, for tests and tools)"""
+    _fields_ = [(f, C.c_int32) for f in ('vt', 'ntiles', 'stats_src', 'finalize', 'fin_offset', 'vpb', 'TX')] + \
+               [(f, C.c_uint32) for f in ('partial_gx', 'partial_gy', 'finalize_gx', 'finalize_gy', 'apply_gx', 'apply_gy')]
+
+
+GN_STATS_SOURCES = ('pass', 'part_in', 'rowgroup')        # es_gn_route_info.stats_src indexes it (ES_GN_STATS_*)
+
+
+class AttnRouteInfo(C.Structure):
+    """es_attn_route_info: the instantiation es_attention_f16 / es_attention_f32 launches (es_attention_route_of; host-only)"""
+    _fields_ = [('kernel', C.c_char * 32), ('DP', C.c_int32), ('rows', C.c_int32), ('grid_x', C.c_uint32), ('grid_y', C.c_uint32),
+                ('block', C.c_int32), ('lds', C.c_int32)]
+
+
 class GegluArgs(C.Structure):
     _fields_ = [('h_f32', C.c_void_p), ('M', C.c_int32), ('C4', C.c_int32), ('out_f16', C.c_void_p), ('out_is_f32', C.c_int32)]
 
@@ -238,6 +253,8 @@ EXPORTS = {
     'es_pack_conv_f32': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     'es_conv_f32': (C.c_int, [C.POINTER(ConvArgs), C.c_void_p]),
     'es_attention_f32': (C.c_int, [C.POINTER(AttnArgs), C.c_void_p]),
+    'es_groupnorm_route_of': (C.c_int, [C.POINTER(GNArgs), C.POINTER(GNRouteInfo)]),
+    'es_attention_route_of': (C.c_int, [C.POINTER(AttnArgs), C.c_int, C.POINTER(AttnRouteInfo)]),
     'es_shape_stem': (C.c_int, [C.POINTER(StemArgs), C.c_void_p]),
     'es_vq_lookup': (C.c_int, [C.POINTER(VQArgs), C.c_void_p]),
     'es_init': (C.c_int, []),

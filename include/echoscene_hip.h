@@ -555,6 +555,37 @@ int es_pack_conv_f32(const float* h_w, int N, int Cin, int taps, float* h_out);
 int es_conv_f32(const es_conv_args* args, es_stream stream);
 int es_attention_f32(const es_attn_args* args, es_stream stream);
 
+/* host-only: every launch decision of es_groupnorm_vol(args) under the process's route options -- the launcher takes each of these
+ * numbers from the same rule (csrc/es_conv_route.h: gn_route).  For tests and tools (tests/side_matrix_cases.py names a route per
+ * case).  Returns 0, or -1 on arguments es_groupnorm_vol refuses (es_last_error(); *out is then untouched).  Launches nothing. */
+enum { ES_GN_STATS_PASS = 0, ES_GN_STATS_PART_IN = 1, ES_GN_STATS_ROWGROUP = 2 };
+typedef struct es_gn_route_info {
+    int32_t vt, ntiles;                 /* voxel tile of the partial sums and tiles per object (whatever the statistics source) */
+    int32_t stats_src;                  /* ES_GN_STATS_PASS: k_gn_partial over x1 / x2; _PART_IN: the producer's partials; _ROWGROUP:
+                                           k_gn_finalize_rg over the producers' row-group sums */
+    int32_t finalize;                   /* 1: k_gn_finalize reduces the tile list once per (object, group) (ntiles > 128), 0: every
+                                           apply block reduces it (gn_reduce_stats), or the row-group route */
+    int32_t fin_offset;                 /* floats from args->stats to the final [O][groups][2] statistics the apply pass reads, -1: none */
+    int32_t vpb;                        /* voxels per apply block */
+    int32_t TX;                         /* lanes across the 8-channel chunks in the apply pass: 1 .. 32 */
+    uint32_t partial_gx, partial_gy;    /* k_gn_partial grid (0, 0: not launched) */
+    uint32_t finalize_gx, finalize_gy;  /* k_gn_finalize / k_gn_finalize_rg grid (0, 0: not launched) */
+    uint32_t apply_gx, apply_gy;        /* k_gn_apply grid */
+} es_gn_route_info;
+int es_groupnorm_route_of(const es_gn_args* args, es_gn_route_info* out);
+/* host-only: the instantiation es_attention_f16(args) (fp32 = 0) or es_attention_f32(args) (fp32 = 1) launches: "attention_32_4_1" ...
+ * "attention_256_4_1" (k_attention<DP, waves, row tiles per wave>), "attention_f32m_64" / "_96" (k_attention_f32m<DP>),
+ * "attention_f32_64" / "_96" (the scalar k_attention_f32<DP>, dhead % 4 != 0).  -1 on arguments the launcher refuses. */
+typedef struct es_attn_route_info {
+    char kernel[32];
+    int32_t DP;                         /* padded head dimension of the instantiation */
+    int32_t rows;                       /* query rows per workgroup */
+    uint32_t grid_x, grid_y;
+    int32_t block;                      /* threads per workgroup */
+    int32_t lds;                        /* dynamic LDS bytes (0: the kernel's LDS is static) */
+} es_attn_route_info;
+int es_attention_route_of(const es_attn_args* args, int fp32, es_attn_route_info* out);
+
 /* VQVAE.decode_no_quant front end (vqvae_networks/network.py:95-103, quantizer.py:68-119): nearest
  * codebook entry per latent voxel; `lut` = codebook already mapped through post_quant_conv. */
 typedef struct es_vq_args {

@@ -269,6 +269,9 @@ def test_conv_fused_skip_and_ncdhw(dev):
 
 
 def test_groupnorm_layernorm_geglu_tocl(dev):
+    """One shape of each element-wise kernel of the volume path, loosely (max error over max value).  Every route of es_groupnorm_vol,
+    to_cl and GEGLU with both output types and the split-operand image are checked per element against fp64, with the route
+    asserted and guarded buffers, in tests/test_hip_groupnorm_matrix.py (cases: tests/side_matrix_cases.py)."""
     from echoscene_amd.plan import Builder
     O, C1, C2, dims = 3, 64, 32, (4, 4, 8)
     V = dims[0] * dims[1] * dims[2]
@@ -344,6 +347,9 @@ def test_gelu_of_the_volume_path_over_its_whole_range(dev):
 
 @pytest.mark.parametrize('Ntok,heads,dh', [(256, 8, 12), (1024, 2, 56), (256, 2, 84), (100, 3, 8)])
 def test_attention(dev, Ntok, heads, dh):
+    """Four shapes against the global maximum.  Every instantiation of k_attention and of the fp32 attention kernels, ragged tiles,
+    short sequences and the input families that steer the online softmax are checked per element against fp64, with the kernel
+    asserted, in tests/test_hip_attention_matrix.py (cases: tests/side_matrix_cases.py)."""
     from echoscene_amd.plan import Builder
     import echoscene_amd.plan_vol  # noqa: F401  (attaches the volume ops to Builder)
     B, Cc = 2, heads * dh
