@@ -807,20 +807,23 @@ int g_rows_family = 1;       // 1 = k_rows_x where it applies (default), 0 = k_l
 
 struct XPlan { int S, Jw, cut[XMAXS + 1], segof[XMAXS], jws[XMAXS]; bool uniform; };
 
-// The K slices of a problem as k_rows_x wants them (every slice inside ONE segment); false = not a problem for k_rows_x
-bool x_plan(const RowsPrep& p, XPlan* xp) {
+// The K slices of a problem as k_rows_x wants them (every slice inside ONE segment); ES_ROWS_FB_NONE, or why it is not a problem for k_rows_x
+int x_plan(const RowsPrep& p, XPlan* xp) {
     const es_linear_args& a = p.a;
-    if (p.nb != 1 || p.csr || a.K % 16) return false;
-    if (p.gepi && !p.has_ln) return false;
-    if (a.res_nslab > XMAXS || a.res2_nslab > XMAXS) return false;
-    int S = 0, koff = 0, maxn = 0;
+    if (p.nb != 1) return ES_ROWS_FB_BATCH;
+    if (p.csr) return ES_ROWS_FB_CSR;
+    if (a.K % 16) return ES_ROWS_FB_K16;
+    if (p.gepi && !p.has_ln) return ES_ROWS_FB_GEGLU_EPI;
+    if (a.res_nslab > XMAXS || a.res2_nslab > XMAXS) return ES_ROWS_FB_RES_SLABS;
+    int S = 0, maxn = 0;
     for (int s = 0; s < a.nseg; ++s) {
         const es_seg& sg = a.seg[s];
-        if (sg.mode != ES_SEG_DIRECT && sg.mode != ES_SEG_GATHER) return false;
-        if (sg.pro != ES_PRO_NONE && sg.pro != ES_PRO_GN && sg.pro != ES_PRO_GN_SILU && sg.pro != ES_PRO_LN && sg.pro != ES_PRO_LN_ATTN) return false;
-        if (sg.step || sg.nslab > 6 || sg.width % 16) return false;
-        if ((sg.pro == ES_PRO_GN || sg.pro == ES_PRO_GN_SILU) && sg.gs < 4) return false;
-        koff += sg.width;
+        if (sg.mode != ES_SEG_DIRECT && sg.mode != ES_SEG_GATHER) return ES_ROWS_FB_CSR;
+        if (sg.pro != ES_PRO_NONE && sg.pro != ES_PRO_GN && sg.pro != ES_PRO_GN_SILU && sg.pro != ES_PRO_LN && sg.pro != ES_PRO_LN_ATTN) return ES_ROWS_FB_PROLOGUE;
+        if (sg.step) return ES_ROWS_FB_STEP;
+        if (sg.nslab > 6) return ES_ROWS_FB_SEG_SLABS;
+        if (sg.width % 16) return ES_ROWS_FB_K16;
+        if ((sg.pro == ES_PRO_GN || sg.pro == ES_PRO_GN_SILU) && sg.gs < 4) return ES_ROWS_FB_PROLOGUE;
     }
     {
         // k_rows_x addresses its operands with 32-bit byte offsets inside a 2 GiB buffer window: an operand whose extent
@@ -830,10 +833,10 @@ bool x_plan(const RowsPrep& p, XPlan* xp) {
             const es_seg& sg = a.seg[s];
             const long rows = sg.mode == ES_SEG_DIRECT ? a.M : 0;
             const long ext = (rows * sg.ld + sg.width) * 4 + (long)(sg.nslab > 1 ? sg.nslab - 1 : 0) * sg.slab_stride * 4;
-            if (ext >= lim) return false;
+            if (ext >= lim) return ES_ROWS_FB_EXTENT;
         }
         const long oext = ((long)a.M * a.out_ld + a.N) * 4;
-        if (oext >= lim || (a.res && ((long)a.M * a.res_ld + a.N) * 4 >= lim) || (a.res2 && ((long)a.M * a.res2_ld + a.N) * 4 >= lim)) return false;
+        if (oext >= lim || (a.res && ((long)a.M * a.res_ld + a.N) * 4 >= lim) || (a.res2 && ((long)a.M * a.res2_ld + a.N) * 4 >= lim)) return ES_ROWS_FB_EXTENT;
     }
     const int nkb = a.K / 16;
     if (a.seg_slices) {
@@ -842,7 +845,7 @@ bool x_plan(const RowsPrep& p, XPlan* xp) {
             const int w = a.seg[s].width / 16;
             const int kbs = (a.seg_slices >> (1 + s)) & 1 ? (p.kbps + 1) / 2 : p.kbps;
             for (int c = 0; c < w; c += kbs) {
-                if (S >= XMAXS) return false;
+                if (S >= XMAXS) return ES_ROWS_FB_SLICES;
                 xp->cut[S] = kb + c; xp->segof[S] = s;
                 const int n = (w - c < kbs) ? w - c : kbs;
                 maxn = n > maxn ? n : maxn;
@@ -854,7 +857,7 @@ bool x_plan(const RowsPrep& p, XPlan* xp) {
     } else {
         // legacy uniform cuts: usable when no slice straddles a segment boundary
         S = p.S;
-        if (S > XMAXS) return false;
+        if (S > XMAXS) return ES_ROWS_FB_SLICES;
         for (int i = 0; i < S; ++i) {
             const int k0 = i * p.kbps, k1 = (i + 1) * p.kbps < nkb ? (i + 1) * p.kbps : nkb;
             int so = -1, c0 = 0;
@@ -863,24 +866,24 @@ bool x_plan(const RowsPrep& p, XPlan* xp) {
                 if (k0 >= c0 && k1 <= c1) so = s;
                 c0 = c1;
             }
-            if (so < 0) return false;
+            if (so < 0) return ES_ROWS_FB_STRADDLE;
             xp->cut[i] = k0; xp->segof[i] = so;
             maxn = (k1 - k0) > maxn ? (k1 - k0) : maxn;
         }
         xp->cut[S] = nkb;
     }
-    if (S != p.S) return false;
+    if (S != p.S) return ES_ROWS_FB_STRADDLE;
     int Jw = (maxn + NKG - 1) / NKG;
     bool gs32 = false;
     for (int s = 0; s < a.nseg; ++s) gs32 = gs32 || ((a.seg[s].pro == ES_PRO_GN || a.seg[s].pro == ES_PRO_GN_SILU) && a.seg[s].gs == 32);
     if (gs32 && (Jw & 1)) ++Jw;
     xp->uniform = true;
     for (int i = 0; i + 1 < S; ++i) xp->uniform = xp->uniform && (xp->cut[i + 1] - xp->cut[i] == xp->cut[1] - xp->cut[0]);
-    if (p.lnattn && S != 1) return false;
+    if (p.lnattn && S != 1) return ES_ROWS_FB_LN_SHAPE;
     if (p.has_ln) {
-        if (S > 2 || S * Jw > 4 || p.nsmax > 2) return false;
-        if (S == 2 && xp->cut[2] - xp->cut[1] != xp->cut[1] - xp->cut[0]) return false;
-    } else if (Jw > 12) return false;
+        if (S > 2 || S * Jw > 4 || p.nsmax > 2) return ES_ROWS_FB_LN_SHAPE;
+        if (S == 2 && xp->cut[2] - xp->cut[1] != xp->cut[1] - xp->cut[0]) return ES_ROWS_FB_LN_SHAPE;
+    } else if (Jw > 12) return ES_ROWS_FB_JW;
     xp->S = S; xp->Jw = Jw;
     // per slice: k-blocks per wave (an even count under 32-channel GroupNorm groups: a group is two adjacent blocks of one wave)
     for (int i = 0; i < S; ++i) {
@@ -889,7 +892,7 @@ bool x_plan(const RowsPrep& p, XPlan* xp) {
         if ((sg.pro == ES_PRO_GN || sg.pro == ES_PRO_GN_SILU) && sg.gs == 32 && (j & 1)) ++j;
         xp->jws[i] = p.has_ln ? Jw : j;
     }
-    return true;
+    return ES_ROWS_FB_NONE;
 }
 
 void x_fill(XProb& P, const RowsPrep& pr, const XPlan& xp) {
@@ -920,18 +923,16 @@ void x_fill(XProb& P, const RowsPrep& pr, const XPlan& xp) {
     }
 }
 
-// the prefetch descriptor of the hinted next launch (w == NULL when there is none or it is not a single-problem k_rows_x launch)
-XPre x_prefetch_of_next() {
+// the prefetch descriptor for the plan's next rows op (w == NULL when there is none or it is not a single-problem k_rows_x launch)
+XPre x_prefetch_of(const es_linear_args* nx) {
     XPre pf;
     memset(&pf, 0, sizeof(pf));
-    const es_linear_args* nx = g_rows_next;
-    g_rows_next = nullptr;
     static const char* pre_env = getenv("ES_ROWS_PREFETCH");        // timing-only: 0 = no prefetch wave
     if (!nx || (pre_env && atoi(pre_env) == 0)) return pf;
     RowsPrep pr;
     if (rows_prepare(nx, &pr)) return pf;
     XPlan xp;
-    if (!x_plan(pr, &xp)) return pf;
+    if (x_plan(pr, &xp) != ES_ROWS_FB_NONE) return pf;
     const int nct = (pr.a.N + 15) / 16;
     const int nt = (pr.has_ln && pr.gepi && xp.S == 1 && nct % 2 == 0) ? 2 : 1;
     pf.w = (const char*)pr.a.wpack;
@@ -944,116 +945,118 @@ XPre x_prefetch_of_next() {
     return pf;
 }
 
-template <int NP>
-int x_launch_np(const void* fn, const XLaunch<NP>& L, dim3 grid, es_stream stream) {
-    void* kargs[] = {(void*)&L};
-    ES_CHECK_HIP(hipLaunchKernel(fn, grid, dim3(NTHREAD + (L.pf.w ? 64 : 0)), kargs, 0, (hipStream_t)stream));
-    ES_CHECK_HIP(hipGetLastError());
-    return 0;
+// ---- the instantiations of the two kernels, one list -----------------------------------------------------------------------------------
+struct RowsKernel { int family; int tp[8]; const void* fn; };
+#define ES_XK(JW, NS, PROC, SLN, NT, GE, NP, G) {1, {JW, NS, PROC, SLN, NT, GE, NP, G}, (const void*)k_rows_x<JW, NS, PROC, SLN, NT, (GE) != 0, NP, (G) != 0>}
+#define ES_LK(NS, PROC, CSR, LNU, GE, U1, NT) {0, {NS, PROC, CSR, LNU, GE, U1, NT, 0}, (const void*)k_linear_rows<NS, PROC, (CSR) != 0, LNU, (GE) != 0, (U1) != 0, NT>}
+const RowsKernel kRowsKernels[] = {
+    // k_rows_x, one problem: [class][GroupNorm compiled in]; the classes of long K ranges (the feed-forward output product, the
+    // triple-row products of the GCNs, the cross-attention-vector product) have no GroupNorm variant
+    ES_XK(2, 4, 0, 1, 1, 0, 1, 0), ES_XK(2, 4, 1, 1, 1, 0, 1, 0), ES_XK(4, 4, 0, 1, 1, 0, 1, 0), ES_XK(4, 4, 1, 1, 1, 0, 1, 0),
+    ES_XK(8, 2, 0, 1, 1, 0, 1, 0), ES_XK(12, 1, 0, 1, 1, 0, 1, 0),
+    // up to three problems
+    ES_XK(2, 4, 0, 1, 1, 0, 3, 0), ES_XK(2, 4, 1, 1, 1, 0, 3, 0), ES_XK(4, 4, 0, 1, 1, 0, 3, 0), ES_XK(4, 4, 1, 1, 1, 0, 3, 0),
+    ES_XK(8, 2, 0, 1, 1, 0, 3, 0),
+    // gathered rows: the triple-row products of the GCNs (plain operands), the wide node vectors of the set-up GCNs (1344 + 640 + 1344)
+    ES_XK(8, 2, 0, 1, 1, 0, 1, 1), ES_XK(8, 2, 0, 1, 1, 0, 3, 1), ES_XK(12, 1, 0, 1, 1, 0, 1, 1), ES_XK(12, 1, 0, 1, 1, 0, 3, 1),
+    // LayerNorm (one / two slices, one / two column tiles) and the formed row
+    ES_XK(4, 2, 2, 1, 1, 1, 1, 0), ES_XK(4, 2, 2, 1, 2, 1, 1, 0), ES_XK(2, 2, 2, 2, 1, 1, 1, 0), ES_XK(4, 2, 3, 1, 1, 1, 1, 0),
+    ES_XK(4, 2, 3, 1, 2, 1, 1, 0),
+    // k_linear_rows: lean instantiations for what the sampling path launches -- plain [slab bound][GroupNorm] --, one general kernel
+    // per slab bound for the rest, LayerNorm [row length][slab bound] with one and two column tiles, CSR, and the
+    // two-workgroups-per-CU variants (stage_chunk U1) of the plain family for launches of more than one round
+    ES_LK(1, 0, 0, 0, 0, 0, 1), ES_LK(1, 1, 0, 0, 0, 0, 1), ES_LK(2, 0, 0, 0, 0, 0, 1), ES_LK(2, 1, 0, 0, 0, 0, 1),
+    ES_LK(4, 0, 0, 0, 0, 0, 1), ES_LK(4, 1, 0, 0, 0, 0, 1), ES_LK(8, 0, 0, 0, 0, 0, 1), ES_LK(8, 1, 0, 0, 0, 0, 1),
+    ES_LK(1, 2, 1, 0, 1, 0, 1), ES_LK(2, 2, 1, 0, 1, 0, 1), ES_LK(4, 2, 1, 0, 1, 0, 1), ES_LK(8, 2, 1, 0, 1, 0, 1),
+    ES_LK(1, 0, 0, 4, 1, 0, 1), ES_LK(2, 0, 0, 4, 1, 0, 1), ES_LK(1, 0, 0, 8, 1, 0, 1), ES_LK(2, 0, 0, 8, 1, 0, 1),
+    ES_LK(1, 0, 0, 4, 1, 0, 2), ES_LK(2, 0, 0, 4, 1, 0, 2), ES_LK(1, 0, 0, 8, 1, 0, 2), ES_LK(2, 0, 0, 8, 1, 0, 2),
+    ES_LK(1, 0, 1, 0, 0, 0, 1),
+    ES_LK(1, 0, 0, 0, 0, 1, 1), ES_LK(1, 1, 0, 0, 0, 1, 1), ES_LK(2, 0, 0, 0, 0, 1, 1), ES_LK(2, 1, 0, 0, 0, 1, 1),
+    ES_LK(4, 0, 0, 0, 0, 1, 1), ES_LK(4, 1, 0, 0, 0, 1, 1)};
+#undef ES_XK
+#undef ES_LK
+constexpr int kNumRowsKernels = (int)(sizeof(kRowsKernels) / sizeof(kRowsKernels[0]));
+static_assert(kNumRowsKernels == 47, "rows kernels: 20 of k_rows_x, 27 of k_linear_rows");
+
+// index of the instantiation with these template parameters, -1: the library holds none
+int rows_kernel_of(int family, int t0, int t1, int t2, int t3, int t4, int t5, int t6, int t7) {
+    const int t[8] = {t0, t1, t2, t3, t4, t5, t6, t7};
+    for (int k = 0; k < kNumRowsKernels; ++k)
+        if (kRowsKernels[k].family == family && memcmp(kRowsKernels[k].tp, t, sizeof(t)) == 0) return k;
+    return -1;
 }
 
-// -1: not launched (the caller falls back to k_linear_rows)
-int x_launch(const RowsPrep* pr, int n, es_stream stream, const RowsLaunch& RL, int gx, int gy) {
-    const bool dry = n == 0;                              // n == 0: would pr[0] launch alone?  -2 = yes, -1 = no
-    if (dry) n = 1;
+void rows_kernel_name(int k, char* out, size_t cap) {
+    const int* t = kRowsKernels[k].tp;
+    if (kRowsKernels[k].family == 1) snprintf(out, cap, "k_rows_x<%d,%d,%d,%d,%d,%d,%d,%d>", t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7]);
+    else snprintf(out, cap, "k_linear_rows<%d,%d,%d,%d,%d,%d,%d>", t[0], t[1], t[2], t[3], t[4], t[5], t[6]);
+}
+
+// ---- routing: every launch decision of the rows products is taken here, on the host, before anything is launched ------------------------
+// One launch of the route.  Both families: the problems pr[first .. first + n), the kernel, grid / block / dynamic LDS and the
+// tile bookkeeping of every problem (RowsLaunch's comment).  Family 1: the slices of every problem and the prefetch descriptor.
+struct RouteLaunch {
+    int family, kernel, first, n, fallback;
+    unsigned gx, gy, gz;
+    int block, ldx;
+    size_t lds;
+    int wg0[3], ny[3], xw[3], fw[3];
     XPlan xp[3];
+    XPre pf;
+};
+struct RowsRoute { int nlaunch; RouteLaunch l[3]; };
+
+// The k_rows_x instantiation that takes pr[0 .. n) as ONE launch, with their slices in xp and the column tiles per workgroup in *nt;
+// -1 with the reason in *why when there is none.
+int x_route(const RowsPrep* pr, int n, XPlan* xp, int* nt, int* why) {
     int jmax = 1, nsmax = 1, proc = 0;
-    bool has_ln = false;
+    bool has_ln = false, gather = false;
+    *nt = 1;
     for (int i = 0; i < n; ++i) {
-        if (!x_plan(pr[i], &xp[i])) return -1;
+        if ((*why = x_plan(pr[i], &xp[i])) != ES_ROWS_FB_NONE) return -1;
         jmax = xp[i].Jw > jmax ? xp[i].Jw : jmax;
         nsmax = pr[i].nsmax > nsmax ? pr[i].nsmax : nsmax;
         proc = pr[i].proc > proc ? pr[i].proc : proc;
         has_ln = has_ln || pr[i].has_ln;
+        for (int sgi = 0; sgi < pr[i].a.nseg; ++sgi) gather = gather || pr[i].a.seg[sgi].mode == ES_SEG_GATHER;
     }
-    if (proc > 1) return -1;
-    bool gather = false;
-    for (int i = 0; i < n; ++i) for (int sgi = 0; sgi < pr[i].a.nseg; ++sgi) gather = gather || pr[i].a.seg[sgi].mode == ES_SEG_GATHER;
-    // kernel classes by load budget (k-blocks per wave, slabs): (2, 6), (4, 2), (8, 1)
+    if (proc > 1) { *why = ES_ROWS_FB_PROLOGUE; return -1; }
+    if (has_ln) {
+        if (n != 1 || gather) { *why = ES_ROWS_FB_LN_SHAPE; return -1; }
+        const RowsPrep& p0 = pr[0];
+        const bool nt2 = p0.gepi && xp[0].S == 1 && ((p0.a.N + 15) / 16) % 2 == 0;
+        *nt = nt2 ? 2 : 1;
+        if (p0.lnattn) return rows_kernel_of(1, 4, 2, 3, 1, *nt, 1, 1, 0);
+        if (xp[0].S == 2) return rows_kernel_of(1, 2, 2, 2, 2, 1, 1, 1, 0);
+        return rows_kernel_of(1, 4, 2, 2, 1, *nt, 1, 1, 0);
+    }
+    // kernel classes by load budget (k-blocks per wave, slabs)
+    static const int cls_jw[4] = {2, 4, 8, 12}, cls_ns[4] = {4, 4, 2, 1};
     int cls = -1;
     if (jmax <= 2 && nsmax <= 4) cls = 0;
     else if (jmax <= 4 && nsmax <= 4) cls = 1;
     else if (jmax <= 8 && nsmax <= 2) cls = 2;
     else if (jmax <= 12 && nsmax <= 1 && (n == 1 || gather)) cls = 3;          // (the cross-attention-vector product: K 1280 in one slice)
-    const void* fn = nullptr;
-    dim3 grid;
-    int nt = 1;
-    if (has_ln) {
-        if (n != 1 || gather) return -1;
-        const RowsPrep& p0 = pr[0];
-        const bool nt2 = p0.gepi && xp[0].S == 1 && ((p0.a.N + 15) / 16) % 2 == 0;
-        nt = nt2 ? 2 : 1;
-        if (p0.lnattn) fn = nt2 ? (const void*)k_rows_x<4, 2, 3, 1, 2, true, 1> : (const void*)k_rows_x<4, 2, 3, 1, 1, true, 1>;
-        else if (xp[0].S == 2) fn = (const void*)k_rows_x<2, 2, 2, 2, 1, true, 1>;
-        else fn = nt2 ? (const void*)k_rows_x<4, 2, 2, 1, 2, true, 1> : (const void*)k_rows_x<4, 2, 2, 1, 1, true, 1>;
-    } else {
-        if (cls < 0) return -1;
-        // [class][GroupNorm compiled in]; the third class (long single-segment K ranges: the feed-forward output product, the
-        // triple-row products of the GCNs) has no GroupNorm variant
-        static const void* const tab1[4][2] = {
-            {(const void*)k_rows_x<2, 4, 0, 1, 1, false, 1>, (const void*)k_rows_x<2, 4, 1, 1, 1, false, 1>},
-            {(const void*)k_rows_x<4, 4, 0, 1, 1, false, 1>, (const void*)k_rows_x<4, 4, 1, 1, 1, false, 1>},
-            {(const void*)k_rows_x<8, 2, 0, 1, 1, false, 1>, nullptr},
-            {(const void*)k_rows_x<12, 1, 0, 1, 1, false, 1>, nullptr}};
-        static const void* const tab3[3][2] = {
-            {(const void*)k_rows_x<2, 4, 0, 1, 1, false, 3>, (const void*)k_rows_x<2, 4, 1, 1, 1, false, 3>},
-            {(const void*)k_rows_x<4, 4, 0, 1, 1, false, 3>, (const void*)k_rows_x<4, 4, 1, 1, 1, false, 3>},
-            {(const void*)k_rows_x<8, 2, 0, 1, 1, false, 3>, nullptr}};
-        fn = n == 1 ? tab1[cls][proc] : cls < 3 ? tab3[cls][proc] : nullptr;
-        if (gather) {        // gathered rows: the triple-row products of the GCNs (plain operands)
-            if (proc != 0) return -1;
-            if (jmax <= 8 && nsmax <= 2) fn = n == 1 ? (const void*)k_rows_x<8, 2, 0, 1, 1, false, 1, true> : (const void*)k_rows_x<8, 2, 0, 1, 1, false, 3, true>;
-            else if (jmax <= 12 && nsmax <= 1)       // (the wide node vectors of the set-up GCNs: 1344 + 640 + 1344 columns)
-                fn = n == 1 ? (const void*)k_rows_x<12, 1, 0, 1, 1, false, 1, true> : (const void*)k_rows_x<12, 1, 0, 1, 1, false, 3, true>;
-            else return -1;
-        }
-        if (!fn) return -1;
+    if (cls < 0) { *why = ES_ROWS_FB_CLASS; return -1; }
+    const int np = n == 1 ? 1 : 3;
+    int k = rows_kernel_of(1, cls_jw[cls], cls_ns[cls], proc, 1, 1, 0, np, 0);
+    if (gather) {
+        if (proc != 0) { *why = ES_ROWS_FB_GATHER; return -1; }
+        if (jmax <= 8 && nsmax <= 2) k = rows_kernel_of(1, 8, 2, 0, 1, 1, 0, np, 1);
+        else if (jmax <= 12 && nsmax <= 1) k = rows_kernel_of(1, 12, 1, 0, 1, 1, 0, np, 1);
+        else { *why = ES_ROWS_FB_GATHER; return -1; }
     }
-    if (dry) return -2;
-    int launch_id = 0;
-    (void)launch_id;
-#ifdef ES_STAMP
-    launch_id = g_rows_stamp ? g_rows_launch_id++ : 0;
-#endif
-    const XPre pf = x_prefetch_of_next();
-    if (n == 1) {
-        XLaunch<1> L;
-        memset(&L, 0, sizeof(L));
-        x_fill(L.p[0], pr[0], xp[0]);
-        L.n = 1;
-        L.pf = pf;
-        grid = dim3((unsigned)(((pr[0].a.N + 15) / 16) / nt * xp[0].S), (unsigned)((pr[0].a.M + MT - 1) / MT), 1);
-        L.p[0].ny = (int)grid.y; L.p[0].xw = (int)grid.x;
-        if (grid.x >= 5461) return -1;
-#ifdef ES_STAMP
-        L.stamp = g_rows_stamp; L.launch_id = launch_id;
-        if (g_rows_stamp && g_rows_log) fprintf(g_rows_log, "%d %d %d %d  x M%d K%d N%d S%d Jw%d ns%d proc%d%s\n", launch_id, (int)grid.x, (int)(grid.y * grid.z), n,
-                                                pr[0].a.M, pr[0].a.K, pr[0].a.N, xp[0].S, xp[0].Jw, nsmax, proc, has_ln ? " ln" : "");
-#endif
-        return x_launch_np<1>(fn, L, grid, stream);
-    }
-    if (gx >= 5461) return -1;                       // (the slice lookup of a multi-problem launch divides by multiplication)
-    XLaunch<3> L;
-    memset(&L, 0, sizeof(L));
-    for (int i = 0; i < n; ++i) {
-        x_fill(L.p[i], pr[i], xp[i]);
-        L.p[i].wg0 = RL.wg0[i]; L.p[i].ny = RL.ny[i]; L.p[i].xw = RL.xw[i]; L.p[i].fw = RL.fw[i];
-    }
-    for (int i = n; i < 3; ++i) L.p[i].wg0 = 0x7fffffff;
-    L.n = n;
-    L.pf = pf;
-    grid = dim3((unsigned)gx, (unsigned)gy, 1);
-#ifdef ES_STAMP
-    L.stamp = g_rows_stamp; L.launch_id = launch_id;
-    if (g_rows_stamp && g_rows_log) fprintf(g_rows_log, "%d %d %d %d  x M%d K%d N%d S%d Jw%d ns%d proc%d multi\n", launch_id, (int)grid.x, (int)grid.y, n,
-                                            pr[0].a.M, pr[0].a.K, pr[0].a.N, xp[0].S, xp[0].Jw, nsmax, proc);
-#endif
-    return x_launch_np<3>(fn, L, grid, stream);
+    if (k < 0) *why = ES_ROWS_FB_CLASS;
+    return k;
 }
 
-int rows_launch(const RowsPrep* pr, int n, es_stream stream) {
-    RowsLaunch L;
-    memset(&L, 0, sizeof(L));
+// The route of the group pr[0 .. n) (problems first .. of the call): one launch, or -- a group k_rows_x does not take as a whole while
+// it takes a member -- n single launches, each on the route it takes alone (a product's bits must not depend on what it is fused
+// with).  *next: the plan's next rows op; the first k_rows_x launch of the route takes it as its prefetch hint.
+int rows_route(const RowsPrep* pr, int n, int first, const es_linear_args** next, RowsRoute* R) {
+    RouteLaunch l;
+    memset(&l, 0, sizeof(l));
+    l.first = first; l.n = n;
     int nsmax = 1, proc = 0, kcmax = 16, gx = 0, gy = 1, wg_real = 0;
     bool csr = false, has_ln = false, gepi = false;
     for (int i = 0; i < n; ++i) {
@@ -1061,13 +1064,12 @@ int rows_launch(const RowsPrep* pr, int n, es_stream stream) {
         gy = ny > gy ? ny : gy;
     }
     for (int i = 0; i < n; ++i) {
-        L.p[i] = pr[i].a; L.S[i] = pr[i].S; L.kbps[i] = pr[i].kbps;
-        L.wg0[i] = gx;
-        L.ny[i] = (pr[i].a.M + MT - 1) / MT;
-        L.xw[i] = ((pr[i].a.N + 15) / 16) * pr[i].S;
-        L.fw[i] = (n > 1 && L.ny[i] < gy) ? (L.xw[i] * L.ny[i] + gy - 1) / gy : 0;      // fewer row tiles than the launch: folded
-        gx += L.fw[i] > 0 ? L.fw[i] : L.xw[i];
-        wg_real += L.xw[i] * L.ny[i];
+        l.wg0[i] = gx;
+        l.ny[i] = (pr[i].a.M + MT - 1) / MT;
+        l.xw[i] = ((pr[i].a.N + 15) / 16) * pr[i].S;
+        l.fw[i] = (n > 1 && l.ny[i] < gy) ? (l.xw[i] * l.ny[i] + gy - 1) / gy : 0;      // fewer row tiles than the launch: folded
+        gx += l.fw[i] > 0 ? l.fw[i] : l.xw[i];
+        wg_real += l.xw[i] * l.ny[i];
         nsmax = pr[i].nsmax > nsmax ? pr[i].nsmax : nsmax;
         proc = pr[i].proc > proc ? pr[i].proc : proc;
         csr = csr || pr[i].csr; has_ln = has_ln || pr[i].has_ln; gepi = gepi || pr[i].gepi;
@@ -1076,25 +1078,36 @@ int rows_launch(const RowsPrep* pr, int n, es_stream stream) {
     }
     ES_REQUIRE(n == 1 || (!has_ln && !gepi && pr[0].nb == 1 && pr[1].nb == 1 && (n < 3 || pr[2].nb == 1)),
                "es_linear_rows_multi_f32: fused problems take no LayerNorm prologue, no GEGLU epilogue and no batching");
-    L.n = n;
-    L.ldx = kcmax + 8;
-    // two column tiles per workgroup (NT = 2) for the GEGLU projection behind a LayerNorm: timing-only switch ES_ROWS_NT2 (0 = off)
-    static const char* nt2_env = getenv("ES_ROWS_NT2");
-    const bool nt2 = n == 1 && has_ln && gepi && pr[0].nb == 1 && pr[0].S == 1 && ((pr[0].a.N + 15) / 16) % 2 == 0 &&
-                     !(nt2_env && atoi(nt2_env) == 0);
     if (g_rows_family == 1) {
-        const int rc = x_launch(pr, n, stream, L, gx, gy);
-        if (rc >= 0) return rc;
+        int nt = 1;
+        int k = x_route(pr, n, l.xp, &nt, &l.fallback);
+        if (k >= 0) {
+            l.pf = x_prefetch_of(*next);
+            *next = nullptr;                         // (taken, whether or not the grid check below lets the launch stay here)
+            if (n == 1) {
+                l.gx = (unsigned)(((pr[0].a.N + 15) / 16) / nt * l.xp[0].S); l.gy = (unsigned)l.ny[0];
+                l.xw[0] = (int)l.gx;
+            } else {
+                l.gx = (unsigned)gx; l.gy = (unsigned)gy;
+            }
+            // (the slice lookup divides by multiplication: exact below 5461 tiles)
+            if (l.gx >= 5461) { k = -1; l.fallback = ES_ROWS_FB_GRID; }
+        }
+        if (k >= 0) {
+            l.family = 1; l.kernel = k; l.gz = 1; l.block = NTHREAD + (l.pf.w ? 64 : 0);
+            R->l[R->nlaunch++] = l;
+            return 0;
+        }
         if (n > 1) {
-            // a group k_rows_x does not take as a whole: every problem takes the route it would take alone (a product's bits must not
-            // depend on what it is fused with) -- unless none of them is a k_rows_x problem, then the group stays one k_linear_rows launch
             bool any = false;
-            for (int i = 0; i < n; ++i) { XPlan xp; any = any || (x_plan(pr[i], &xp) && x_launch(pr + i, 0, stream, L, 0, 0) == -2); }
-            if (any) {
-                for (int i = 0; i < n; ++i) if (int rc1 = rows_launch(pr + i, 1, stream)) return rc1;
+            for (int i = 0; i < n; ++i) { XPlan x1; int nt1, why1; any = any || x_route(pr + i, 1, &x1, &nt1, &why1) >= 0; }
+            if (any) {       // (unless none of them is a k_rows_x problem: then the group stays one k_linear_rows launch)
+                for (int i = 0; i < n; ++i) if (int rc1 = rows_route(pr + i, 1, first + i, next, R)) return rc1;
                 return 0;
             }
         }
+        l.xw[0] = ((pr[0].a.N + 15) / 16) * pr[0].S;
+        memset(&l.pf, 0, sizeof(l.pf));
     }
     for (int i = 0; i < n; ++i)
         ES_REQUIRE(!pr[i].lnattn, "es_linear_rows_f32: ES_PRO_LN_ATTN runs on the register-operand kernel only (K=%d, %d slabs, kernel family %d): "
@@ -1108,70 +1121,119 @@ int rows_launch(const RowsPrep* pr, int n, es_stream stream) {
             ES_REQUIRE((a.seg[sgi].width / 16) % pr[i].kbps == 0,
                        "es_linear_rows_f32: segment-aligned slices of %d k-blocks do not tile segment %d (%d columns) and the problem is not one k_rows_x handles", pr[i].kbps, sgi, a.seg[sgi].width);
     }
+    // two column tiles per workgroup (NT = 2) for the GEGLU projection behind a LayerNorm: timing-only switch ES_ROWS_NT2 (0 = off)
+    static const char* nt2_env = getenv("ES_ROWS_NT2");
+    const bool nt2 = n == 1 && has_ln && gepi && pr[0].nb == 1 && pr[0].S == 1 && ((pr[0].a.N + 15) / 16) % 2 == 0 &&
+                     !(nt2_env && atoi(nt2_env) == 0);
     if (nt2) gx /= 2;
-    const size_t lds = (size_t)(MT * L.ldx + (nt2 ? 2 : 1) * NWAVE * 256) * sizeof(float);
-    dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)pr[0].nb);
-    // kernel table: lean instantiations for what the sampling path launches, one general kernel per slab bound for the rest
-    static const void* const k_plain[4][2] = {
-        {(const void*)k_linear_rows<1, 0, false, 0, false>, (const void*)k_linear_rows<1, 1, false, 0, false>},
-        {(const void*)k_linear_rows<2, 0, false, 0, false>, (const void*)k_linear_rows<2, 1, false, 0, false>},
-        {(const void*)k_linear_rows<4, 0, false, 0, false>, (const void*)k_linear_rows<4, 1, false, 0, false>},
-        {(const void*)k_linear_rows<8, 0, false, 0, false>, (const void*)k_linear_rows<8, 1, false, 0, false>}};
-    static const void* const k_general[4] = {
-        (const void*)k_linear_rows<1, 2, true, 0, true>, (const void*)k_linear_rows<2, 2, true, 0, true>,
-        (const void*)k_linear_rows<4, 2, true, 0, true>, (const void*)k_linear_rows<8, 2, true, 0, true>};
-    static const void* const k_ln[2][2] = {
-        {(const void*)k_linear_rows<1, 0, false, 4, true>, (const void*)k_linear_rows<2, 0, false, 4, true>},
-        {(const void*)k_linear_rows<1, 0, false, 8, true>, (const void*)k_linear_rows<2, 0, false, 8, true>}};
-    static const void* const k_ln_nt2[2][2] = {
-        {(const void*)k_linear_rows<1, 0, false, 4, true, false, 2>, (const void*)k_linear_rows<2, 0, false, 4, true, false, 2>},
-        {(const void*)k_linear_rows<1, 0, false, 8, true, false, 2>, (const void*)k_linear_rows<2, 0, false, 8, true, false, 2>}};
-    static const void* const k_csr = (const void*)k_linear_rows<1, 0, true, 0, false>;
-    // two-workgroups-per-CU variants (stage_chunk U1) of the plain family for launches of more than one round
-    static const void* const k_plain_u1[3][2] = {
-        {(const void*)k_linear_rows<1, 0, false, 0, false, true>, (const void*)k_linear_rows<1, 1, false, 0, false, true>},
-        {(const void*)k_linear_rows<2, 0, false, 0, false, true>, (const void*)k_linear_rows<2, 1, false, 0, false, true>},
-        {(const void*)k_linear_rows<4, 0, false, 0, false, true>, (const void*)k_linear_rows<4, 1, false, 0, false, true>}};
-    const int nsi = nsmax <= 1 ? 0 : nsmax <= 2 ? 1 : nsmax <= 4 ? 2 : 3;
+    l.family = 0;
+    l.ldx = kcmax + 8;
+    l.lds = (size_t)(MT * l.ldx + (nt2 ? 2 : 1) * NWAVE * 256) * sizeof(float);
+    l.gx = (unsigned)gx; l.gy = (unsigned)gy; l.gz = (unsigned)pr[0].nb;
+    l.block = NTHREAD;
+    const int nsi = nsmax <= 1 ? 0 : nsmax <= 2 ? 1 : nsmax <= 4 ? 2 : 3, ns = 1 << nsi;
     static const char* u1_env = getenv("ES_ROWS_U1");            // timing-only A/B switch: 0 = never, 2 = every fused plain launch
     const int u1_mode = u1_env ? atoi(u1_env) : 1;
     // default rule: a FUSED launch of more than 256 workgroups whose ordinary variant holds one workgroup per CU (GroupNorm
     // prologue or 4-slab operands: 146-194 VGPRs): two per CU run 257-512 workgroups in ONE round instead of two
     const bool one_per_cu = proc == 1 || nsi == 2;
     const bool u1 = n > 1 && nsi <= 2 && (u1_mode == 2 || (u1_mode == 1 && one_per_cu && wg_real > 256));
-    const void* fn = nullptr;
-    if (has_ln) fn = (nt2 ? k_ln_nt2 : k_ln)[pr[0].a.K <= 512 ? 0 : 1][nsi];
-    else if (csr && proc == 0 && nsmax == 1 && !gepi) fn = k_csr;
-    else if (!csr && proc <= 1 && !gepi) fn = u1 ? k_plain_u1[nsi][proc] : k_plain[nsi][proc];
-    else fn = k_general[nsi];
-    {   // one-off per process, thread-safe: dynamic LDS limit (a 1024-column chunk needs 73 KiB)
-        static std::once_flag once;
-        static hipError_t attr_err = hipSuccess;
-        std::call_once(once, [] {
-            constexpr int bytes = (MT * (KCH + 8) + 2 * NWAVE * 256) * 4;
-            auto set = [](const void* f) {
-                const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-                if (e != hipSuccess && attr_err == hipSuccess) attr_err = e;
-            };
-            for (int i = 0; i < 4; ++i) { set(k_plain[i][0]); set(k_plain[i][1]); set(k_general[i]); }
-            for (int i = 0; i < 3; ++i) { set(k_plain_u1[i][0]); set(k_plain_u1[i][1]); }
-            for (int i = 0; i < 2; ++i) { set(k_ln[i][0]); set(k_ln[i][1]); set(k_ln_nt2[i][0]); set(k_ln_nt2[i][1]); }
-            set(k_csr);
-        });
-        ES_REQUIRE(attr_err == hipSuccess, "es_linear_rows_f32: hipFuncSetAttribute failed: %s", hipGetErrorString(attr_err));
+    if (has_ln) l.kernel = rows_kernel_of(0, ns, 0, 0, pr[0].a.K <= 512 ? 4 : 8, 1, 0, nt2 ? 2 : 1, 0);
+    else if (csr && proc == 0 && nsmax == 1 && !gepi) l.kernel = rows_kernel_of(0, 1, 0, 1, 0, 0, 0, 1, 0);
+    else if (!csr && proc <= 1 && !gepi) l.kernel = rows_kernel_of(0, ns, proc, 0, 0, 0, u1 ? 1 : 0, 1, 0);
+    else l.kernel = rows_kernel_of(0, ns, 2, 1, 0, 1, 0, 1, 0);
+    ES_REQUIRE(l.kernel >= 0, "es_linear_rows_f32: no k_linear_rows instantiation for %d slabs, prologue class %d", nsmax, proc);
+    R->l[R->nlaunch++] = l;
+    return 0;
+}
+
+template <int NP>
+int x_launch(const RowsPrep* pr, const RouteLaunch& l, es_stream stream) {
+    XLaunch<NP> L;
+    memset(&L, 0, sizeof(L));
+    for (int i = 0; i < l.n; ++i) {
+        x_fill(L.p[i], pr[l.first + i], l.xp[i]);
+        L.p[i].wg0 = l.wg0[i]; L.p[i].ny = l.ny[i]; L.p[i].xw = l.xw[i]; L.p[i].fw = l.fw[i];
     }
-    static const char* dbg_env = getenv("ES_ROWS_DBG");          // ablation switches of tools/microbench_rows.py (1: no weight loads, 2: no staging)
-    L.dbg = dbg_env ? atoi(dbg_env) : 0;
+    for (int i = l.n; i < NP; ++i) L.p[i].wg0 = 0x7fffffff;
+    L.n = l.n;
+    L.pf = l.pf;
 #ifdef ES_STAMP
     L.stamp = g_rows_stamp;
     L.launch_id = g_rows_stamp ? g_rows_launch_id++ : 0;
-    if (g_rows_stamp && g_rows_log) fprintf(g_rows_log, "%d %d %d %d  M%d K%d N%d S%d ns%d proc%d%s%s%s\n", L.launch_id, (int)grid.x, (int)grid.y, n,
-                                            pr[0].a.M, pr[0].a.K, pr[0].a.N, pr[0].S, nsmax, proc, has_ln ? " ln" : "", csr ? " csr" : "", u1 ? " u1" : "");
+    if (g_rows_stamp && g_rows_log) {
+        char name[56];
+        rows_kernel_name(l.kernel, name, sizeof(name));
+        fprintf(g_rows_log, "%d %d %d %d  x M%d K%d N%d S%d Jw%d %s\n", L.launch_id, (int)l.gx, (int)l.gy, l.n, pr[l.first].a.M, pr[l.first].a.K,
+                pr[l.first].a.N, l.xp[0].S, l.xp[0].Jw, name);
+    }
 #endif
     void* kargs[] = {(void*)&L};
-    ES_CHECK_HIP(hipLaunchKernel(fn, grid, dim3(NTHREAD), kargs, lds, (hipStream_t)stream));
+    ES_CHECK_HIP(hipLaunchKernel(kRowsKernels[l.kernel].fn, dim3(l.gx, l.gy, l.gz), dim3((unsigned)l.block), kargs, 0, (hipStream_t)stream));
     ES_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+// launches what the route names; decides nothing
+int rows_launch(const RowsPrep* pr, const RowsRoute& R, es_stream stream) {
+    for (int li = 0; li < R.nlaunch; ++li) {
+        const RouteLaunch& l = R.l[li];
+        if (l.family == 1) {
+            // (single-problem kernels read a 3x smaller argument block)
+            if (int rc = kRowsKernels[l.kernel].tp[6] == 1 ? x_launch<1>(pr, l, stream) : x_launch<3>(pr, l, stream)) return rc;
+            continue;
+        }
+        RowsLaunch L;
+        memset(&L, 0, sizeof(L));
+        for (int i = 0; i < l.n; ++i) {
+            const RowsPrep& p = pr[l.first + i];
+            L.p[i] = p.a; L.S[i] = p.S; L.kbps[i] = p.kbps;
+            L.wg0[i] = l.wg0[i]; L.ny[i] = l.ny[i]; L.xw[i] = l.xw[i]; L.fw[i] = l.fw[i];
+        }
+        L.n = l.n;
+        L.ldx = l.ldx;
+        {   // one-off per process, thread-safe: dynamic LDS limit (a 1024-column chunk needs 73 KiB)
+            static std::once_flag once;
+            static hipError_t attr_err = hipSuccess;
+            std::call_once(once, [] {
+                constexpr int bytes = (MT * (KCH + 8) + 2 * NWAVE * 256) * 4;
+                for (int k = 0; k < kNumRowsKernels; ++k) {
+                    if (kRowsKernels[k].family != 0) continue;
+                    const hipError_t e = hipFuncSetAttribute(kRowsKernels[k].fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+                    if (e != hipSuccess && attr_err == hipSuccess) attr_err = e;
+                }
+            });
+            ES_REQUIRE(attr_err == hipSuccess, "es_linear_rows_f32: hipFuncSetAttribute failed: %s", hipGetErrorString(attr_err));
+        }
+        static const char* dbg_env = getenv("ES_ROWS_DBG");          // ablation switches of tools/microbench_rows.py (1: no weight loads, 2: no staging)
+        L.dbg = dbg_env ? atoi(dbg_env) : 0;
+#ifdef ES_STAMP
+        L.stamp = g_rows_stamp;
+        L.launch_id = g_rows_stamp ? g_rows_launch_id++ : 0;
+        if (g_rows_stamp && g_rows_log) {
+            char name[56];
+            rows_kernel_name(l.kernel, name, sizeof(name));
+            fprintf(g_rows_log, "%d %d %d %d  M%d K%d N%d S%d %s\n", L.launch_id, (int)l.gx, (int)l.gy, l.n, pr[l.first].a.M, pr[l.first].a.K,
+                    pr[l.first].a.N, pr[l.first].S, name);
+        }
+#endif
+        void* kargs[] = {(void*)&L};
+        ES_CHECK_HIP(hipLaunchKernel(kRowsKernels[l.kernel].fn, dim3(l.gx, l.gy, l.gz), dim3((unsigned)l.block), kargs, l.lds, (hipStream_t)stream));
+        ES_CHECK_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+// prepare, route, launch: the body of the two launch calls
+int rows_run(const es_linear_args* const* args, int n, es_stream stream) {
+    const es_linear_args* next = g_rows_next;
+    g_rows_next = nullptr;          // the hint lives for ONE launch call, whichever kernel took it (it points into the caller's plan)
+    RowsPrep pr[3];
+    for (int i = 0; i < n; ++i) if (int rc = rows_prepare(args[i], &pr[i])) return rc;
+    RowsRoute R;
+    R.nlaunch = 0;
+    if (int rc = rows_route(pr, n, 0, &next, &R)) return rc;
+    return rows_launch(pr, R, stream);
 }
 }  // namespace
 
@@ -1181,9 +1243,57 @@ extern "C" int es_linear_rows_takes_ln_attn(const es_linear_args* a) {
     RowsPrep pr;
     if (rows_prepare(a, &pr)) return -1;
     if (!pr.lnattn || g_rows_family != 1) return 0;
-    RowsLaunch L;
-    memset(&L, 0, sizeof(L));
-    return x_launch(&pr, 0, nullptr, L, 0, 0) == -2 ? 1 : 0;
+    XPlan xp;
+    int nt, why;
+    return x_route(&pr, 1, &xp, &nt, &why) >= 0 ? 1 : 0;
+}
+
+extern "C" int es_linear_rows_route_of(const es_linear_args* const* args, int n, const es_linear_args* next, es_rows_route_info* out) {
+    if (!(args && out && n >= 1 && n <= 3)) { es_set_error("es_linear_rows_route_of: n=%d (1..3)", n); return -1; }
+    RowsPrep pr[3];
+    for (int i = 0; i < n; ++i) if (rows_prepare(args[i], &pr[i])) return -1;
+    RowsRoute R;
+    R.nlaunch = 0;
+    if (rows_route(pr, n, 0, &next, &R)) return -1;
+    es_rows_route_info info;
+    memset(&info, 0, sizeof(info));
+    info.nlaunch = R.nlaunch;
+    for (int li = 0; li < R.nlaunch; ++li) {
+        const RouteLaunch& l = R.l[li];
+        es_rows_route_launch& o = info.launch[li];
+        o.family = l.family; o.kernel = l.kernel;
+        for (int i = 0; i < 8; ++i) o.tparam[i] = kRowsKernels[l.kernel].tp[i];
+        rows_kernel_name(l.kernel, o.name, sizeof(o.name));
+        o.first = l.first; o.nprob = l.n;
+        o.grid_x = l.gx; o.grid_y = l.gy; o.grid_z = l.gz; o.block = l.block; o.lds = (int32_t)l.lds;
+        o.fallback = l.family == 0 ? l.fallback : ES_ROWS_FB_NONE;
+        if (l.pf.w) {
+            o.pf_gx = l.pf.gx; o.pf_nt = l.pf.nt; o.pf_nkb_total = l.pf.nkb_total; o.pf_S = l.pf.smagic & 0xffff;
+            for (int i = 0; i <= o.pf_S; ++i) o.pf_cut[i] = l.pf.cut[i];
+        }
+        for (int i = 0; i < l.n; ++i) {
+            es_rows_route_prob& q = o.prob[i];
+            q.S = pr[l.first + i].S; q.kbps = pr[l.first + i].kbps;
+            q.wg0 = l.wg0[i]; q.ny = l.ny[i]; q.xw = l.xw[i]; q.fw = l.fw[i];
+            if (l.family == 1) {
+                const XPlan& xp = l.xp[i];
+                q.Jw = xp.Jw;
+                for (int s = 0; s <= xp.S; ++s) q.cut[s] = xp.cut[s];
+                for (int s = 0; s < xp.S; ++s) q.jws[s] = xp.jws[s];
+            }
+        }
+    }
+    *out = info;
+    return 0;
+}
+
+extern "C" int es_rows_kernel_count(void) { return kNumRowsKernels; }
+
+extern "C" const char* es_rows_kernel_name(int index) {
+    static char names[kNumRowsKernels][56];
+    static std::once_flag once;
+    std::call_once(once, [] { for (int i = 0; i < kNumRowsKernels; ++i) rows_kernel_name(i, names[i], sizeof(names[i])); });
+    return index >= 0 && index < kNumRowsKernels ? names[index] : nullptr;
 }
 
 extern "C" int es_rows_get_kernel_family(void) { return g_rows_family; }
@@ -1195,20 +1305,13 @@ extern "C" int es_rows_set_kernel_family(int family) {
 }
 
 extern "C" int es_linear_rows_f32(const es_linear_args* a_in, es_stream stream) {
-    RowsPrep pr;
-    if (int rc = rows_prepare(a_in, &pr)) { g_rows_next = nullptr; return rc; }
-    const int rc = rows_launch(&pr, 1, stream);
-    g_rows_next = nullptr;          // the hint lives for ONE launch call, whichever kernel took it (it points into the caller's plan)
-    return rc;
+    return rows_run(&a_in, 1, stream);
 }
 
 extern "C" int es_linear_rows_multi_f32(const es_linear_args* const* args, int n, es_stream stream) {
+    if (!(args && n >= 1 && n <= 3)) g_rows_next = nullptr;
     ES_REQUIRE(args && n >= 1 && n <= 3, "es_linear_rows_multi_f32: n=%d (1..3)", n);
-    RowsPrep pr[3];
-    for (int i = 0; i < n; ++i) if (int rc = rows_prepare(args[i], &pr[i])) { g_rows_next = nullptr; return rc; }
-    const int rc = rows_launch(pr, n, stream);
-    g_rows_next = nullptr;
-    return rc;
+    return rows_run(args, n, stream);
 }
 
 extern "C" int es_row_select(const es_rowsel_args* a, es_stream stream) {

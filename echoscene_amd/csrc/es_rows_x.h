@@ -117,7 +117,12 @@ __device__ __forceinline__ void x_row_stats(const f4 (&a)[NB], int nb, int Jw, i
     float S[NKG], Q[NKG], tot = 0.f;
 #pragma unroll
     for (int w = 0; w < NKG; ++w) { S[w] = buf[w * 16 + i16]; Q[w] = buf[NKG * 16 + w * 16 + i16]; tot += S[w]; }
+    // (a ROUNDED product, which an intrinsic does not promise under -ffp-contract=fast: left to the compiler, tot * inv_k was fused into some of the later subtractions x - mean in one instantiation
+    //  and into none in another -- k_rows_x<4,2,3,1,2> against <4,2,3,1,1> -- and the two gave different bits for the same row)
     mean = tot * inv_k;
+    asm volatile("" : "+v"(mean));                           // (no instruction: the product is a value in a register from here on)
+    // (the other products below -- 2 d (S - n p), n d d, m2 * inv_k + eps -- are still the compiler's to contract; that every instantiation
+    //  contracts them alike is what tests/test_hip_rows_matrix.py::test_two_column_tiles_per_workgroup_equal_one holds them to)
     float m2 = 0.f;
 #pragma unroll
     for (int w = 0; w < NKG; ++w) {
@@ -376,6 +381,7 @@ __global__ __launch_bounds__(NTHREAD + 64) void k_rows_x(const XLaunch<NP> L) {
         for (int w = 0; w < NKG; ++w) tot += lnx[w * 16 + i16];
         const float inv_k = P.inv_k;
         mean = tot * inv_k;
+        asm volatile("" : "+v"(mean));                       // (rounded, as in x_row_stats: the same bits in every instantiation)
         float sq = 0.f;
 #pragma unroll
         for (int v = 0; v < NB; ++v) {

@@ -112,6 +112,31 @@ class AttnRouteInfo(C.Structure):
                 ('block', C.c_int32), ('lds', C.c_int32)]
 
 
+class RowsRouteProb(C.Structure):
+    """es_rows_route_prob: the numbers of one problem of a rows launch"""
+    _fields_ = [('S', C.c_int32), ('kbps', C.c_int32), ('Jw', C.c_int32), ('cut', C.c_int32 * 7), ('jws', C.c_int32 * 6),
+                ('wg0', C.c_int32), ('ny', C.c_int32), ('xw', C.c_int32), ('fw', C.c_int32)]
+
+
+class RowsRouteLaunch(C.Structure):
+    """es_rows_route_launch: one launch of a rows route"""
+    _fields_ = [('family', C.c_int32), ('kernel', C.c_int32), ('tparam', C.c_int32 * 8), ('name', C.c_char * 56),
+                ('first', C.c_int32), ('nprob', C.c_int32), ('grid_x', C.c_uint32), ('grid_y', C.c_uint32), ('grid_z', C.c_uint32),
+                ('block', C.c_int32), ('lds', C.c_int32), ('fallback', C.c_int32),
+                ('pf_gx', C.c_int32), ('pf_nt', C.c_int32), ('pf_nkb_total', C.c_int32), ('pf_S', C.c_int32), ('pf_cut', C.c_int32 * 7),
+                ('prob', RowsRouteProb * 3)]
+
+
+class RowsRouteInfo(C.Structure):
+    """es_rows_route_info: every launch decision of es_linear_rows_f32 / es_linear_rows_multi_f32 (es_linear_rows_route_of; host-only)"""
+    _fields_ = [('nlaunch', C.c_int32), ('launch', RowsRouteLaunch * 3)]
+
+
+# es_rows_route_launch.fallback indexes it (ES_ROWS_FB_*)
+ROWS_FALLBACKS = ('none', 'batch', 'csr', 'k16', 'geglu_epi', 'res_slabs', 'prologue', 'step', 'seg_slabs', 'extent', 'slices', 'straddle',
+                  'ln_shape', 'jw', 'class', 'gather', 'grid')
+
+
 class GegluArgs(C.Structure):
     _fields_ = [('h_f32', C.c_void_p), ('M', C.c_int32), ('C4', C.c_int32), ('out_f16', C.c_void_p), ('out_is_f32', C.c_int32)]
 
@@ -210,6 +235,9 @@ EXPORTS = {
     'es_linear_rows_slices': (C.c_int, [C.POINTER(LinearArgs), C.POINTER(C.c_int)]),
     'es_linear_rows_takes_ln_attn': (C.c_int, [C.POINTER(LinearArgs)]),
     'es_linear_rows_auto_slices': (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    'es_linear_rows_route_of': (C.c_int, [C.POINTER(C.POINTER(LinearArgs)), C.c_int, C.POINTER(LinearArgs), C.POINTER(RowsRouteInfo)]),
+    'es_rows_kernel_count': (C.c_int, []),
+    'es_rows_kernel_name': (C.c_char_p, [C.c_int]),
     'es_row_select': (C.c_int, [C.POINTER(RowSelArgs), C.c_void_p]),
     'es_ddpm_update': (C.c_int, [C.POINTER(UpdateArgs), C.c_void_p]),
     'es_ddim_update': (C.c_int, [C.POINTER(UpdateArgs), C.c_void_p]),

@@ -173,6 +173,58 @@ int es_linear_rows_slices(const es_linear_args* args, int* kb_per_slice);
 /* host-only: 1 when a launch with an ES_PRO_LN_ATTN segment (es_seg.pro) would run, 0 when the library has no kernel for its shape
  * (the planner then keeps the self-attention product as a launch of its own), -1 on invalid arguments */
 int es_linear_rows_takes_ln_attn(const es_linear_args* args);
+/* host-only: every launch decision of es_linear_rows_f32 (n = 1) / es_linear_rows_multi_f32 (n = 1..3) for these problems under the
+ * process's kernel family, with `next` (may be NULL) the plan's next rows op, i.e. the prefetch hint of the launch -- the launchers
+ * take each of these numbers from the same rule (csrc/es_rows.hip: rows_route).  For tests and tools (tests/rows_matrix_cases.py
+ * names a route per case); kernel, grid and prefetch are no part of the numerics contract, S / cuts / Jw are.  Returns 0, or -1 where
+ * the launcher refuses (its own message in es_last_error(); *out is then untouched).  Launches nothing, dereferences no operand. */
+enum { ES_ROWS_FB_NONE = 0,       /* why a launch is on k_linear_rows although the process's family is 1 (k_rows_x): */
+       ES_ROWS_FB_BATCH = 1,      /* a batched launch                                                                */
+       ES_ROWS_FB_CSR = 2,        /* a CSR pooling segment                                                           */
+       ES_ROWS_FB_K16 = 3,        /* K, or a segment's width, is no multiple of 16                                   */
+       ES_ROWS_FB_GEGLU_EPI = 4,  /* GEGLU epilogue without a LayerNorm prologue                                     */
+       ES_ROWS_FB_RES_SLABS = 5,  /* a residual of more than 6 slabs                                                 */
+       ES_ROWS_FB_PROLOGUE = 6,   /* SiLU / GEGLU prologue                                                           */
+       ES_ROWS_FB_STEP = 7,       /* a step-indexed segment                                                          */
+       ES_ROWS_FB_SEG_SLABS = 8,  /* a segment of more than 6 slabs                                                  */
+       ES_ROWS_FB_EXTENT = 9,     /* an operand reaches past the 2 GiB buffer window                                 */
+       ES_ROWS_FB_SLICES = 10,    /* more than 6 slices                                                              */
+       ES_ROWS_FB_STRADDLE = 11,  /* a uniform cut straddles two segments                                            */
+       ES_ROWS_FB_LN_SHAPE = 12,  /* LayerNorm rows the register kernel does not hold (> 512 columns, > 2 slices ...) */
+       ES_ROWS_FB_JW = 13,        /* more than 12 k-blocks per wave in a slice                                       */
+       ES_ROWS_FB_CLASS = 14,     /* no kernel class for (k-blocks per wave, slabs, GroupNorm)                       */
+       ES_ROWS_FB_GATHER = 15,    /* gathered rows with GroupNorm or more than 2 slabs                               */
+       ES_ROWS_FB_GRID = 16,      /* 5461 or more tiles along grid x (the slice lookup divides by multiplication)    */
+       ES_ROWS_FB_COUNT = 17 };
+typedef struct es_rows_route_prob {
+    int32_t S, kbps;                    /* slices (= output slabs) and the rounded kb_per_slice */
+    int32_t Jw;                         /* family 1: k-blocks per wave, the bound over the slices (0 under family 0) */
+    int32_t cut[7];                     /* family 1: first k-block of every slice, and the end (family 0 cuts at the multiples of kbps: zeros) */
+    int32_t jws[6];                     /* family 1: k-blocks per wave of every slice */
+    int32_t wg0, ny, xw, fw;            /* first tile along grid x, row tiles, tiles per row (column tiles x slices), folded width (0: not folded) */
+} es_rows_route_prob;
+typedef struct es_rows_route_launch {
+    int32_t family;                     /* 1: k_rows_x, 0: k_linear_rows */
+    int32_t kernel;                     /* index into es_rows_kernel_name() */
+    int32_t tparam[8];                  /* family 1: JW, NS, PROC, SLN, NT, GEGLU_EPI, NP, GATHER; family 0: NS, PROC, CSR, LNU, GEGLU_EPI, U1, NT, 0 */
+    char name[56];                      /* "k_rows_x<2,4,0,1,1,0,1,0>" / "k_linear_rows<1,0,0,0,0,0,1>": built from tparam */
+    int32_t first, nprob;               /* the problems args[first .. first + nprob) */
+    uint32_t grid_x, grid_y, grid_z;
+    int32_t block;                      /* 512, or 576 with the prefetch wave */
+    int32_t lds;                        /* dynamic LDS bytes (family 1: 0, its LDS is static) */
+    int32_t fallback;                   /* ES_ROWS_FB_*: family 0 under the process's family 1 */
+    int32_t pf_gx, pf_nt, pf_nkb_total, pf_S;     /* the prefetch descriptor: all zero when the ninth wave is not launched */
+    int32_t pf_cut[7];
+    es_rows_route_prob prob[3];
+} es_rows_route_launch;
+typedef struct es_rows_route_info {
+    int32_t nlaunch;                    /* 1, or n when a group of n problems splits into single launches */
+    es_rows_route_launch launch[3];
+} es_rows_route_info;
+int es_linear_rows_route_of(const es_linear_args* const* args, int n, const es_linear_args* next, es_rows_route_info* out);
+/* the instantiations of the two rows kernels that the library holds: their count, and the name of each as es_rows_route_launch spells it */
+int es_rows_kernel_count(void);
+const char* es_rows_kernel_name(int index);
 /* the library's default kb_per_slice for a [*, K] x [K, N] product whose slices must be multiples of kalign_cols columns
  * (~256 workgroups per 32 rows, >= 128 columns per slice, <= 8 slabs); 0 = do not split */
 int es_linear_rows_auto_slices(int K, int N, int kalign_cols);

@@ -42,6 +42,7 @@ def test_struct_sizes_match_header(L, tmp_path):
              'es_tocl_args': hip.ToClArgs, 'es_stem_args': hip.StemArgs, 'es_vq_args': hip.VQArgs,
              'es_rowsel_args': hip.RowSelArgs, 'es_conv_route_info': hip.ConvRouteInfo,
              'es_gn_route_info': hip.GNRouteInfo, 'es_attn_route_info': hip.AttnRouteInfo,
+             'es_rows_route_prob': hip.RowsRouteProb, 'es_rows_route_launch': hip.RowsRouteLaunch, 'es_rows_route_info': hip.RowsRouteInfo,
              'es_op': hip.Op}
     src = '#include <stdio.h>\n#include "echoscene_hip.h"\nint main(){' + ''.join(
         'printf("%s %%zu\\n", sizeof(%s));' % (n, n) for n in names) + 'return 0;}'
@@ -56,29 +57,33 @@ def test_struct_sizes_match_header(L, tmp_path):
 
 
 def test_route_info_layouts_match_header(L, tmp_path):
-    """es_gn_route_info / es_attn_route_info (es_groupnorm_route_of, es_attention_route_of): every field of the ctypes mirrors sits
-    at the offset and has the size the C compiler gives it, and the statistics sources are numbered as the header's enum"""
+    """es_gn_route_info / es_attn_route_info / es_rows_route_info with its two member structs (es_groupnorm_route_of,
+    es_attention_route_of, es_linear_rows_route_of): every field of the ctypes mirrors sits at the offset and has the size the C compiler
+    gives it, and the statistics sources and the rows fall-back reasons are numbered as the header's enums"""
     import subprocess
     from echoscene_amd import hip
-    structs = {'es_gn_route_info': hip.GNRouteInfo, 'es_attn_route_info': hip.AttnRouteInfo}
+    structs = {'es_gn_route_info': hip.GNRouteInfo, 'es_attn_route_info': hip.AttnRouteInfo, 'es_rows_route_prob': hip.RowsRouteProb,
+               'es_rows_route_launch': hip.RowsRouteLaunch, 'es_rows_route_info': hip.RowsRouteInfo}
     prints = ''.join('printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s*)0)->%s));' % (n, f[0], n, f[0], n, f[0])
                      for n, cls in structs.items() for f in cls._fields_)
     src = '#include <stdio.h>\n#include <stddef.h>\n#include "echoscene_hip.h"\nint main(){' + prints + \
-          'printf("src %d %d %d\\n", ES_GN_STATS_PASS, ES_GN_STATS_PART_IN, ES_GN_STATS_ROWGROUP);return 0;}'
+          'printf("fb' + ' %d' * len(hip.ROWS_FALLBACKS) + ' %d\\n", ' + ', '.join('ES_ROWS_FB_' + f.upper() for f in hip.ROWS_FALLBACKS) + \
+          ', ES_ROWS_FB_COUNT);printf("src %d %d %d\\n", ES_GN_STATS_PASS, ES_GN_STATS_PART_IN, ES_GN_STATS_ROWGROUP);return 0;}'
     c = tmp_path / 'off.c'
     c.write_text(src)
     exe = tmp_path / 'off'
     subprocess.check_call(['gcc', '-I', os.path.join(ROOT, 'include'), str(c), '-o', str(exe)])
     lines = [ln.split() for ln in subprocess.check_output([str(exe)]).decode().strip().split('\n')]
-    got = {ln[0]: (int(ln[1]), int(ln[2])) for ln in lines[:-1]}
+    got = {ln[0]: (int(ln[1]), int(ln[2])) for ln in lines[:-2]}
     n_fields = 0
     for n, cls in structs.items():
         for f in cls._fields_:
             d = getattr(cls, f[0])
             assert got['%s.%s' % (n, f[0])] == (d.offset, d.size), (n, f[0], got['%s.%s' % (n, f[0])], (d.offset, d.size))
             n_fields += 1
-    assert n_fields == len(got) == 13 + 7
+    assert n_fields == len(got) == 13 + 7 + 9 + 18 + 2
     assert [int(v) for v in lines[-1][1:]] == [hip.GN_STATS_SOURCES.index(s) for s in ('pass', 'part_in', 'rowgroup')]
+    assert [int(v) for v in lines[-2][1:]] == list(range(len(hip.ROWS_FALLBACKS) + 1))
 
 
 def test_rows_slice_choice_depends_on_k_and_n_only(L):
