@@ -169,11 +169,7 @@ def norm_segs(views, gamma, beta, eps, silu, C=None, groups=32, b=None, M=None):
         a.x2, a.C2 = (views[1].ptr, views[1].width) if len(views) > 1 else (None, 0)
         a.O, a.V, a.groups, a.eps = M, 1, groups, eps
         a.gamma, a.beta, a.silu = gamma.data_ptr(), beta.data_ptr(), 1 if silu else 0
-        st = getattr(b, '_gn_stats', None)           # (Builder.groupnorm's scratch: one for all GroupNorms of a plan, same stream)
-        need = M * groups * 2 + M * groups * 2
-        if st is None or st.numel() < need:
-            st = b._gn_stats = b.buf(need, scratch=True)
-        a.stats = st.data_ptr()
+        a.stats = b.gn_scratch(M * groups * 2 + M * groups * 2).data_ptr()     # (one for all GroupNorms of a plan, same stream)
         a.y_f16, a.y_is_f32 = y.data_ptr(), 1
         b.keep += [gamma, beta, y] + [v.t for v in views]
         b._push(hip.OP_GN, 'gn', a)
@@ -398,10 +394,26 @@ class Rider:
         self.done = True
 
 
-class Builder:
-    """Accumulates ops + keeps every referenced device tensor alive."""
+# (plan_vol takes this module's names only after it has defined VolEmitters, and only those defined above this line)
+from .plan_vol import VolEmitters       # noqa: E402
 
-    def __init__(self, device):
+
+class Builder(VolEmitters):
+    """Accumulates ops + keeps every referenced device tensor alive.  The rows-path emitters are defined here, the volume-path
+    ones in plan_vol.VolEmitters; every field either of them reads is declared in __init__."""
+
+    def __init__(self, device, precision='fp16', o_hint=0, up_fold=False, shard_block=None, force_exchange=False):
+        # -- hints of the volume path (plan_vol), given when the builder is made --
+        assert precision in ('fp16', 'fp32', 'fp32x'), precision
+        self.precision = precision            # operand precision of the volume ops; VolEmitters.fp32 / .fp32x derive from it
+        self.o_hint = int(o_hint or 0)        # object sharding: tile / split choices of the whole problem (> 0) / of the reference shard (< 0)
+        self.up_fold = bool(up_fold)          # up-sampling convs carry their folded weight image (12 taps per parity class, not 27)
+        self.shard_block = shard_block        # rows of this rank's send block of the echo all-gather; None: its own object count
+        self.force_exchange = bool(force_exchange)    # emit the echo exchange although this rank owns every object
+        # -- caches of the volume path --
+        self._ws = None                       # split-K workspace shared by all convs of the plan
+        self._gn_stats = None                 # statistics scratch shared by all GroupNorms of the plan (gn_scratch)
+        self._produced = {}                   # data_ptr of a tensor a conv of this plan wrote -> plan_vol.Produced
         self.device = device
         self.ops = []
         self.keep = []
@@ -652,7 +664,8 @@ class Plan:
         self.n_ops = len(b.ops)
         self.weight_bytes = b.weight_bytes
         self.flops = b.flops
-        self.scratch = set(getattr(b, 'scratch', ()))
+        self.device = b.device
+        self.scratch = set(b.scratch)
         arr = (Op * len(b.ops))(*b.ops)
         self._arr = arr
         self.handle = hip.lib().es_plan_create(arr, len(b.ops))
@@ -694,7 +707,7 @@ class Plan:
 def sub_plan(parent, ops):
     """A plan of ``ops`` -- a slice or a recombination of the op list of ``parent`` (a Builder or a Plan) -- on the parent's buffers: it
     shares ``keep`` and ``tags`` and reports the parent's ``weight_bytes`` / ``flops``; it allocates nothing and claims no scratch."""
-    b = Builder(getattr(parent, 'device', None))
+    b = Builder(parent.device)
     b.ops, b.keep, b.tags = list(ops), parent.keep, parent.tags
     b.weight_bytes, b.flops = parent.weight_bytes, parent.flops
     return b.finish()
@@ -1116,7 +1129,7 @@ def emit_unet1d_step(b, w, g, x, obj_embed_dev, temb, step, eps_out, tables=None
     b.ride(rider)
     if w.enable_t_emb and tables is None:
         b.linear([seg(emb)], w.box_t, O, View(objbuf, col=oe_w + gdim, ld=Dobj, width=gdim))
-    pred = b.pred_rows = b.dev(w.pred_table[torch.from_numpy(g.p_host)])     # refreshed in place for a new graph
+    pred = b.dev(w.pred_table[torch.from_numpy(g.p_host)])     # refreshed in place for a new graph
     ctx = emit_gcn(b, w.gcn, g, View(objbuf), Dobj, View(pred), pred.shape[1], rider=rider)
     box['ctx'] = ctx
     b.tags.update(ctx=ctx, gcn_in=View(objbuf))
@@ -1137,7 +1150,7 @@ def emit_unet1d_step(b, w, g, x, obj_embed_dev, temb, step, eps_out, tables=None
             coff += Cc
     b.join(1)                                  # emb_all (side lane, forked after the time MLP)
     rider.finish()                             # the rest of the trunk
-    return objbuf
+    return objbuf, pred
 
 
 def _trunk(b, w, O, x, emb_all, emb_ld, box, eps_out):

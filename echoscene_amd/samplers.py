@@ -81,9 +81,9 @@ def emit_layout_step(b, w, g, obj_embed, temb, tables, T, coef=None, keep_tab=No
     step = b.buf(1, dtype=torch.int32, zero=True)
     noise = b.buf(T + 1, O, D)
     oe = b.dev(obj_embed)
-    objbuf = emit_unet1d_step(b, w, g, x, oe, temb, step, eps_out, tables=tables)
+    objbuf, pred = emit_unet1d_step(b, w, g, x, oe, temb, step, eps_out, tables=tables)
     eps = b.tags['eps']                                  # View: the output conv's K slices (the update sums the slabs)
-    out = dict(x=x, step=step, noise=noise, objbuf=objbuf, oe_w=oe.shape[1], eps=eps, n_eps_ops=len(b.ops), pred=b.pred_rows)
+    out = dict(x=x, step=step, noise=noise, objbuf=objbuf, oe_w=oe.shape[1], eps=eps, n_eps_ops=len(b.ops), pred=pred)
     if coef is None:
         return out
     draws = View(noise[1:].reshape(T, O * D), ld=O * D)
@@ -107,7 +107,8 @@ def emit_shape_step(b, w, g, uc, temb, tables, coef, keep_tab, S, z_shape, lo, h
     (``step_noise``: eta != 0), or es_plms_update (``plms``; its two first-iteration ops are returned as ``first_ops``, not appended).
     ``keep_vox``: the voxel form of the masked loop (shape completion) -- ``mask`` is [Ol, V], one value per latent voxel, and the one
     op in front of the denoiser is es_ddim_blend_vox instead of es_ddim_blend; everything else is the ``keep`` step.
-    Sharding hints travel as attributes of ``b`` (shard_block, force_exchange, o_hint), as the results of emit_unet3d_step do."""
+    The sharding hints (shard_block, force_exchange, o_hint) and the precision are those ``b`` was made with.  ``temb`` is not read
+    (the time tables hold what it fed); it keeps its place for the callers."""
     keep = bool(keep or keep_vox)
     x = b.buf(hi - lo, *z_shape)
     eps = b.buf(hi - lo, *z_shape)
@@ -118,11 +119,9 @@ def emit_shape_step(b, w, g, uc, temb, tables, coef, keep_tab, S, z_shape, lo, h
         out.update(x0=b.buf(hi - lo, *z_shape, zero=True), mask=b.buf(*mshape, zero=True), knoise=b.buf(S, x.numel(), zero=True))
         (b.blend_vox if keep_vox else b.blend)(x, out['x0'], out['mask'], out['knoise'], keep_tab, step)
     ucd = b.dev(uc)
-    b.xc = b.cdev = b.pred_rows = None                   # (results emit_unet3d_step leaves on the Builder; not every variant has these)
-    out['objbuf'] = emit_unet3d_step(b, w, g, x, ucd, temb, step, eps, dims=z_shape[1:], lo=lo, hi=hi, c_dev=c_local, tables=tables,
-                                     gather_rows=gather_rows)
-    out.update(ucw=ucd.shape[1], n_eps_ops=len(b.ops), split=b.split, codes_local=b.codes_local, codes_all=b.codes_all,
-               code_cols=b.code_cols, xc=b.xc, cdev=b.cdev, pred=b.pred_rows)
+    r = emit_unet3d_step(b, w, g, x, ucd, step, eps, tables, dims=z_shape[1:], lo=lo, hi=hi, c_dev=c_local, gather_rows=gather_rows)
+    out.update(objbuf=r.objbuf, ucw=ucd.shape[1], n_eps_ops=len(b.ops), split=r.split, codes_local=r.codes_local,
+               codes_all=r.codes_all, code_cols=r.code_cols, xc=r.xc, cdev=r.cdev, pred=r.pred_rows)
     if plms:
         # the sampler's state: the last three eps, iteration i in slot i % 3, and x at the start of iteration 0
         ring, xsave = b.buf(3, x.numel(), zero=True), b.buf(x.numel(), zero=True)
@@ -485,12 +484,9 @@ class ShapeDenoiser:
             return new_state(empty=True, x=z(0, *self.z_shape), eps=z(0, *self.z_shape), lo=lo, hi=hi, O=O, codes_local=z(block, 64),
                              codes_all=z(block * self.world, 64), sig=sig, sampler=sampler)
         g = GraphIndex(triples, O, self.device, capacity=cap)
-        b = Builder(self.device)
-        b.shard_block = block
-        b.force_exchange = self.force_exchange
-        b.up_fold = self.up_fold and not self.deterministic
-        if self.deterministic:
-            b.o_hint = -CANON_OBJECTS   # split-K / partial-sum tiling of the reference shard -> bit-identical latents at every world size
+        # deterministic: split-K / partial-sum tiling of the reference shard -> bit-identical latents at every world size
+        b = Builder(self.device, precision=self.precision, o_hint=-CANON_OBJECTS if self.deterministic else 0,
+                    up_fold=self.up_fold and not self.deterministic, shard_block=block, force_exchange=self.force_exchange)
         plms = sampler == 'plms'
         bufs = emit_shape_step(b, self.w, g, uc, self.temb, self.tables, self.coef, self.keep_tab, self.S, self.z_shape, lo, hi,
                                c_local=None if c is None else c[lo:hi], gather_rows=block * self.world, keep=bool(keep), plms=plms,

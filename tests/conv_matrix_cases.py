@@ -108,7 +108,7 @@ def route_label(r):
 
 
 def takes_workspace(case):
-    """the planner's rule (plan_vol.py, VolBuilderMixin.conv): a launch gets the split-K workspace, and splitk = -1 when the caller
+    """the planner's rule (plan_vol.py, VolEmitters.conv): a launch gets the split-K workspace, and splitk = -1 when the caller
     says nothing, only with a channels-last output of at most 8192 x 5376 floats, N % 4 == 0 and no GEGLU epilogue"""
     D, H, W = case['dims']
     return case['out'] != 'ncdhw' and case['O'] * D * H * W * case['N'] <= 8192 * 5376 and case['N'] % 4 == 0 and not case['geglu']

@@ -178,8 +178,7 @@ def dry_shape_ops(**kw):
     O, S = 4, 4
     _, triples = synth.synthetic_graph(O, seed=6)
     g = GraphIndex(triples, O, dev, capacity=_cap(triples.shape[0]))
-    b = Builder(dev)
-    b.shard_block, b.force_exchange, b.up_fold = O, False, True
+    b = Builder(dev, shard_block=O, force_exchange=False, up_fold=True)
     tables = dict(emb=None, emb_all=torch.zeros(S, w.emb_all.N), t_lin=torch.zeros(S, 64))
     out = emit_shape_step(b, w, g, torch.zeros(O, 64), torch.zeros(S, w.mc), tables, torch.zeros(S, 4), torch.zeros(S, 2), S,
                           (3, 16, 16, 16), 0, O, gather_rows=O, **kw)

@@ -63,8 +63,7 @@ for (dims, cin, cout, taps) in SH:
         for k, v in dict(Z, **opts).items():
             setopt(k, v)
         bm = -opts['conv_kw_ks'] if 'conv_kw_ks' in opts else opts.get('conv_st_bm', 0)
-        b = Builder(dev)
-        b.o_hint = oh
+        b = Builder(dev, o_hint=oh)
         x = b.buf(M, cin, dtype=torch.float16); x.copy_(x0)
         out = b.buf(M, cout)
         res = b.buf(M, cout); res.copy_(res0)

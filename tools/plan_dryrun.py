@@ -52,11 +52,8 @@ def emit_shape_step_cpu(O=32, width=224, precision='fp16', up_fold=True, determi
     assert w.precision == precision
     _, triples = synth.synthetic_graph(O, seed=seed)
     g = GraphIndex(triples, O, dev, capacity=_cap(triples.shape[0]))
-    b = Builder(dev)
-    b.shard_block, b.force_exchange = O, False
-    b.up_fold = up_fold and not deterministic
-    if deterministic:
-        b.o_hint = -CANON_OBJECTS
+    b = Builder(dev, precision=precision, o_hint=-CANON_OBJECTS if deterministic else 0, up_fold=up_fold and not deterministic,
+                shard_block=O)
     S = 4
     tables = dict(emb=None, emb_all=torch.zeros(S, w.emb_all.N), t_lin=torch.zeros(S, 64))
     uc = torch.zeros(O, 1280)
