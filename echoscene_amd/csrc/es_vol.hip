@@ -3119,7 +3119,12 @@ extern "C" int es_groupnorm_vol(const es_gn_args* a, es_stream stream) {
 }
 
 extern "C" int es_layernorm_tokens(const es_ln_args* a, es_stream stream) {
+    ES_REQUIRE(a && a->x && a->gamma && a->beta && a->y_f16, "es_layernorm_tokens: NULL argument (x, gamma, beta and y_f16 are required)");
+    ES_REQUIRE(a->M > 0, "es_layernorm_tokens: M=%d rows", a->M);
     ES_REQUIRE(a->C <= 1024 && a->C > 0 && a->C % 4 == 0, "es_layernorm_tokens: C=%d (a multiple of 4, max 1024)", a->C);
+    // 16-byte loads of x, gamma and beta; 16-byte (fp32) or 8-byte (f16) stores of y
+    ES_REQUIRE((((uintptr_t)a->x | (uintptr_t)a->gamma | (uintptr_t)a->beta) & 15) == 0 && ((uintptr_t)a->y_f16 & (a->y_is_f32 ? 15 : 7)) == 0,
+               "es_layernorm_tokens: x, gamma, beta must be 16-byte aligned, y_f16 %d-byte", a->y_is_f32 ? 16 : 8);
     // resident waves loop over the rows: 8 workgroups of 4 waves per CU at most
     long wgs = ((long)a->M + 3) / 4;
     if (wgs > 2048) wgs = 2048;
@@ -3176,19 +3181,25 @@ extern "C" int es_split_f16x3(const float* x, long M, int C, void* out, es_strea
 }
 
 extern "C" int es_shape_stem(const es_stem_args* a, es_stream stream) {
-    const long n1 = (long)a->O * 32 * 512, n2 = (long)a->O * 512;
+    ES_REQUIRE(a && a->x && a->w0 && a->b0 && a->w1 && a->b1 && a->scratch && a->out,
+               "es_shape_stem: NULL argument (x, w0, b0, w1, b1, scratch and out are required)");
+    ES_REQUIRE(a->O > 0, "es_shape_stem: O=%d objects", a->O);
+    ES_REQUIRE(a->Cin == 0 || a->Cin == 3 || a->Cin == 4, "es_shape_stem: Cin=%d (3 or 4; 0 means 3)", a->Cin);
+    ES_REQUIRE(a->x_ostride >= 0, "es_shape_stem: x_ostride=%d", a->x_ostride);
+    ES_REQUIRE(((uintptr_t)a->scratch & 15) == 0, "es_shape_stem: scratch must be 16-byte aligned");       // (k_stem2 stages it with 16-byte loads)
+    const long n2 = (long)a->O * 512;
     const int Cx = a->Cin ? a->Cin : 3;
-    ES_REQUIRE(Cx >= 1 && Cx <= 4, "es_shape_stem: Cin=%d (3 or 4)", Cx);
-    (void)n1;
-    hipLaunchKernelGGL(k_stem1, dim3(64, a->O), dim3(256), (size_t)(Cx * 288 + 32 * Cx * 27) * 4, (hipStream_t)stream, *a);
     static const LdsLimits lim{{(const void*)k_stem2, 32 * 513 * 4}};
     ES_REQUIRE(lim.err == hipSuccess, "es_shape_stem: hipFuncSetAttribute failed: %s", hipGetErrorString(lim.err));
+    hipLaunchKernelGGL(k_stem1, dim3(64, a->O), dim3(256), (size_t)(Cx * 288 + 32 * Cx * 27) * 4, (hipStream_t)stream, *a);
     hipLaunchKernelGGL(k_stem2, dim3((unsigned)((n2 * 8 + 255) / 256)), dim3(256), 32 * 513 * 4, (hipStream_t)stream, *a);
     ES_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
 extern "C" int es_vq_lookup(const es_vq_args* a, es_stream stream) {
+    ES_REQUIRE(a && a->z && a->codebook && a->lut && a->out_f16, "es_vq_lookup: NULL argument (z, codebook, lut and out_f16 are required; idx_out may be NULL)");
+    ES_REQUIRE(a->O > 0 && a->V > 0, "es_vq_lookup: O=%d objects of V=%d voxels", a->O, a->V);
     ES_REQUIRE(a->n_embed > 0 && a->n_embed * 16 <= 160 * 1024 - 1024, "es_vq_lookup: n_embed=%d too large for LDS", a->n_embed);
     ES_REQUIRE(a->Cpad >= 3, "es_vq_lookup: Cpad=%d", a->Cpad);
     static const LdsLimits lim{{(const void*)k_vq_lookup, 160 * 1024 - 1024}};

@@ -305,7 +305,11 @@ extern "C" int es_conv_f32(const es_conv_args* a, es_stream stream) {
     ES_REQUIRE(a->Cin % 16 == 0 && a->Cin > 0, "es_conv_f32: Cin=%d must be a positive multiple of 16", a->Cin);
     ES_REQUIRE(a->taps == 27 || a->taps == 1, "es_conv_f32: taps=%d", a->taps);
     ES_REQUIRE(!a->a2 || (a->Cin2 % 16 == 0 && a->Cin2 > 0), "es_conv_f32: Cin2=%d", a->Cin2);
-    ES_REQUIRE(a->out_f32 && !a->out_f16 && a->epilogue == ES_EPI_NONE && !a->gn_stats_out, "es_conv_f32: fp32 output only, no fused GEGLU / statistics");
+    ES_REQUIRE(a->a && a->w && a->out_f32, "es_conv_f32: NULL argument (a, w and out_f32 are required)");
+    ES_REQUIRE(!a->out_f16, "es_conv_f32: out_f16 given: fp32 output only");
+    ES_REQUIRE(a->epilogue == ES_EPI_NONE && !a->gn_stats_out, "es_conv_f32: epilogue=%d%s: no fused GEGLU / statistics", a->epilogue,
+               a->gn_stats_out ? ", gn_stats_out given" : "");
+    ES_REQUIRE(a->O > 0 && a->N > 0, "es_conv_f32: O=%d N=%d", a->O, a->N);
     Geom32 g;
     g.O = a->O; g.D = a->D; g.H = a->H; g.W = a->W;
     g.Di = a->D; g.Hi = a->H; g.Wi = a->W;

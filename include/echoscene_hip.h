@@ -581,7 +581,9 @@ typedef struct es_ln_args {
     const float* x; int32_t M, C; float eps; const float* gamma; const float* beta; void* y_f16;
     int32_t y_is_f32;     /* 1: y_f16 points at an fp32 tensor (fp32-operand validation route) */
 } es_ln_args;
-int es_layernorm_tokens(const es_ln_args* args, es_stream stream);      /* nn.LayerNorm, attention.py:229-231 */
+/* nn.LayerNorm, attention.py:229-231.  Refused on the host: a NULL x / gamma / beta / y_f16, M <= 0, C not a multiple of 4 in 4..1024,
+ * x / gamma / beta not 16-byte aligned, y_f16 not 8-byte (y_is_f32: 16-byte) aligned. */
+int es_layernorm_tokens(const es_ln_args* args, es_stream stream);
 
 typedef struct es_attn_args {
     const void* qkv;      /* f16 [B*Ntok, 3*C]: q | k | v, heads packed as (h d)                */
@@ -648,6 +650,7 @@ typedef struct es_vq_args {
     int32_t* idx_out;        /* optional [O*V] chosen indices                                    */
     void* out_f16;           /* [O*V, Cpad] channels-last f16                                    */
 } es_vq_args;
+/* Refused on the host: a NULL z / codebook / lut / out_f16 (idx_out may be NULL), O or V <= 0, Cpad < 3, n_embed outside 1..10176. */
 int es_vq_lookup(const es_vq_args* args, es_stream stream);
 
 /* The VQ-VAE encoder's conv_in (Encoder3D, vqvae_modules.py:205-209): Conv3d(1, N, 3, padding 1) over a one-channel volume, fp32 in,
@@ -677,6 +680,7 @@ typedef struct es_stem_args {
     int32_t Cin;           /* 3 ('crossattn': x_t) or 4 ('concat': x_t and the c_s channel); 0 = 3      */
     int32_t x_ostride;     /* floats between objects in x; 0 = Cin * 4096                              */
 } es_stem_args;
+/* Refused on the host: a NULL pointer, O <= 0, Cin other than 0, 3 or 4, a negative x_ostride, a scratch that is not 16-byte aligned. */
 int es_shape_stem(const es_stem_args* args, es_stream stream);
 
 

@@ -24,12 +24,11 @@ options (always restored).  For every launch:
 Measured error ratios and findings: profiles/conv_matrix_notes.md (run with -s to print them)."""
 import ctypes as C
 
-import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 import conv_matrix_cases as cm
+from conv_matrix_ref import cl as _cl, problem as _problem, rnd as _rnd, stray_findings
 from guarded_buffers import INT_OF, GuardedInput, GuardedOutput
 
 pytestmark = pytest.mark.gpu
@@ -43,14 +42,6 @@ def dev():
     return torch.device('cuda')
 
 
-def _rnd(shape, seed, scale=1.0):
-    return torch.randn(shape, generator=torch.Generator().manual_seed(seed), dtype=torch.float32) * scale
-
-
-def _cl(x):          # NCDHW -> [O*V, C]
-    return x.permute(0, 2, 3, 4, 1).reshape(-1, x.shape[1]).contiguous()
-
-
 def _options(L):
     buf = C.create_string_buffer(1024)
     L.es_vol_options(buf, 1024)
@@ -61,55 +52,6 @@ def _set(L, pairs):
     from echoscene_amd import hip
     for k, v in pairs:
         hip.check(L.es_vol_set_option(k.encode(), int(v)), 'es_vol_set_option')
-
-
-def _problem(case):
-    """the operands (fp16-rounded where the kernels take f16), the fp64 reference and e32, the error of the fp32 CPU computation"""
-    O, (D, H, W), Cin, N, taps, mode = case['O'], case['dims'], case['Cin'], case['N'], case['taps'], case['mode']
-    V = D * H * W
-    p = dict(x=_rnd((O, Cin) + cm.input_dims(mode, case['dims']), 1).half().float(),
-             wt=(_rnd((N, Cin, 3, 3, 3) if taps == 27 else (N, Cin), 2) / np.sqrt(Cin * taps)).half().float(), bias=_rnd((N,), 3))
-    if case['rowvec']:
-        p['rowvec'] = _rnd((O, N), 4)
-    if case['res']:
-        p['res'] = _rnd((O * V, N), 5)
-    if case['Cin2']:
-        p['xs'] = _rnd((O, case['Cin2'], D, H, W), 6).half().float()
-        p['ws'] = (_rnd((N, case['Cin2']), 7) / np.sqrt(case['Cin2'])).half().float()
-
-    def compute(dt):
-        x, wt = p['x'].to(dt), p['wt'].to(dt)
-        if taps == 1:
-            y = _cl(x) @ wt.t()
-        else:
-            if mode == cm.SAME:
-                y = F.conv3d(x, wt, padding=1)
-            elif mode == cm.DOWN_HW:
-                y = F.conv3d(x, wt, stride=(1, 2, 2), padding=1)
-            elif mode == cm.DOWN_DHW:
-                y = F.conv3d(x, wt, stride=2, padding=1)
-            elif mode == cm.DOWN_DHW_P01:
-                y = F.conv3d(F.pad(x, (0, 1, 0, 1, 0, 1)), wt, stride=2)
-            else:
-                y = F.conv3d(F.interpolate(x, (D, H, W), mode='nearest'), wt, padding=1)
-            if case['Cin2']:
-                y = y + F.conv3d(p['xs'].to(dt), p['ws'].to(dt)[:, :, None, None, None])
-            y = _cl(y)
-        y = y + p['bias'].to(dt)
-        if case['rowvec']:
-            y = y + p['rowvec'].to(dt).repeat_interleave(V, 0)
-        if case['res']:
-            y = y + p['res'].to(dt)
-        if case['geglu']:
-            y = y[:, :N // 2] * F.gelu(y[:, N // 2:])
-        if case['out'] == 'ncdhw':
-            y = y.reshape(O, V, N).permute(0, 2, 1).reshape(O * N, V).contiguous()
-        return y
-
-    p['ref'] = compute(torch.float64)
-    p['scale'] = p['ref'].abs().max().item()
-    p['e32'] = (compute(torch.float32).double() - p['ref']).abs().max().item() / p['scale']
-    return p
 
 
 @pytest.mark.parametrize('case', cm.CASES, ids=lambda c: c['name'])
@@ -177,20 +119,7 @@ def test_conv_matrix(dev, case):
                 _set(L, found)
             me = dict(kernel=got[0], S=S, o32=o32.view.clone() if o32 else None, o16=o16.view.clone() if o16 else None, st=st)
             # ---- stray writes, unwritten elements
-            for nm, g in guarded:
-                if not g.unchanged():
-                    bad.append('%s: input %s (or its guards) was written' % (tag, nm))
-            for nm, o in (('out_f32', o32), ('out_f16', o16)):
-                if o is None:
-                    continue
-                if not o.guards_unchanged():
-                    bad.append('%s: the guard rows of %s were written' % (tag, nm))
-                fin = torch.isfinite(o.view)
-                if not bool(fin.all()):
-                    rws = (~fin).any(1).nonzero().flatten()
-                    cls = (~fin).any(0).nonzero().flatten()
-                    bad.append('%s: %s holds %d non-finite elements (never written, or computed from a guard): rows %d..%d (%d of them), '
-                               'columns %d..%d (%d of them)' % (tag, nm, int((~fin).sum()), rws[0], rws[-1], len(rws), cls[0], cls[-1], len(cls)))
+            bad += stray_findings(tag, guarded, (('out_f32', o32), ('out_f16', o16)))
             # ---- values against fp64
             if o32 is not None:
                 err = (o32.view.double() - ref).abs()
