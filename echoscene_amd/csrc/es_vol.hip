@@ -473,25 +473,34 @@ __device__ __forceinline__ void split_range(int nks0, int kch2, int taps, int bz
 //     column tiles whose weight slabs fit an L2 together (~3 MiB), so the workgroups that run side by side on an XCD share ONE
 //     activation row tile and a resident weight panel.  With x fastest the 29 MB activation of the 16x8x8 FeedForward
 //     projection was re-fetched once per column tile: rocprofv3 FETCH_SIZE 364 MB per launch (x2-corrected), MFMA busy 0.20.
-__device__ __forceinline__ void conv_tile_of(const es_conv_args& a, int& bx, int& by, int& bz) {
-    const int gx = gridDim.x, gy = gridDim.y;
-    const int nwg = gx * gy * (int)gridDim.z;
-    const int orig = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
+__device__ __forceinline__ int xcd_logical_id(int nwg, int orig) {      // hardware workgroup id orig of nwg -> L, one contiguous range of L per XCD
     const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-    const int L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
+}
+// id t of a gx x gy grid -> (bx, by), COLUMN tiles fastest inside panels of column tiles whose weights (slab bytes each) fit ~3 MiB together
+__device__ __forceinline__ void panel_tile_of(int t, int gx, int gy, long slab, int& bx, int& by) {
+    int npanel = (int)(((long)gy * slab + (3L << 20) - 1) / (3L << 20));
+    npanel = npanel < 1 ? 1 : (npanel > gy ? gy : npanel);
+    const int Pw = (int)((unsigned)(gy + npanel - 1) / (unsigned)npanel);           // column tiles per panel (1 <= npanel <= gy)
+    const int full = gx * Pw;
+    const int p = t / full, rr = t - p * full;
+    const int w = (gy - p * Pw) < Pw ? (gy - p * Pw) : Pw;                          // the last panel may be narrower
+    bx = rr / w;
+    by = p * Pw + (rr - bx * w);
+}
+// this workgroup's K split bz and tile id t (in [0, gx gy)) of a (gx, gy, S) grid
+__device__ __forceinline__ void grid_tile_id(int gx, int gy, int& t, int& bz) {
+    const int L = xcd_logical_id(gx * gy * (int)gridDim.z, blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z));
     const int per_z = gx * gy;
     bz = L / per_z;
-    const int t = L - bz * per_z;
+    t = L - bz * per_z;
+}
+__device__ __forceinline__ void conv_tile_of(const es_conv_args& a, int& bx, int& by, int& bz) {
+    const int gx = gridDim.x, gy = gridDim.y;
+    int t;
+    grid_tile_id(gx, gy, t, bz);
     if (a.taps == 1 && gy >= 2) {
-        const long slab = ((long)a.Cin + (a.a2 ? a.Cin2 : 0)) * BN * 2;                 // bytes of one column tile's weights
-        int npanel = (int)(((long)gy * slab + (3L << 20) - 1) / (3L << 20));
-        npanel = npanel < 1 ? 1 : (npanel > gy ? gy : npanel);
-        const int Pw = (gy + npanel - 1) / npanel;                                      // column tiles per panel
-        const int full = gx * Pw;
-        const int p = t / full, rr = t - p * full;
-        const int w = (gy - p * Pw) < Pw ? (gy - p * Pw) : Pw;                          // the last panel may be narrower
-        bx = rr / w;
-        by = p * Pw + (rr - bx * w);
+        panel_tile_of(t, gx, gy, ((long)a.Cin + (a.a2 ? a.Cin2 : 0)) * BN * 2, bx, by);      // slab: one column tile's weights
     } else {
         bx = t % gx;
         by = t / gx;
@@ -862,6 +871,189 @@ __device__ __forceinline__ unsigned tap_mask27(int cd, int nd, int ch, int nh, i
     return ((vd & 1u) ? m9 : 0u) | ((vd & 2u) ? m9 << 9 : 0u) | ((vd & 4u) ? m9 << 18 : 0u);
 }
 
+// ---------------------------------------------------------------------------------------------
+// The A-tile gather of the implicit-GEMM conv kernels, written once for conv_ws_tile and k_conv_kw (k_conv_lean keeps its own copy, see there): which input voxel a lane's 16-byte piece loads for the K unit
+// (32-channel chunk, tap) being staged -- all conv modes, the fused 1x1 skip phase, the folded taps of k_conv_ws_fold.  The kernels keep
+// what is theirs (ring, LDS destinations, B pieces, waits and barriers) and call rows / start once, then per K unit prep, a_voff per
+// A piece and advance.
+// ---------------------------------------------------------------------------------------------
+// 16-byte slot p of the A tile that starts at row m0: row p >> 2, physical chunk p & 3 of its 64 B (lc: the logical chunk stored there)
+struct ConvRow { int lc, o, d, h, w; long m; bool ok; };      // m: the row (0 past M), ok: row < M
+__device__ __forceinline__ ConvRow conv_row_of(const ConvGeom& g, long m0, long M, int p) {
+    ConvRow r;
+    const int row = p >> 2;
+    r.lc = (p & 3) ^ f_swz(row);
+    const long m = m0 + row;
+    r.ok = m < M;
+    r.m = r.ok ? m : 0;
+    r.w = (int)(r.m & (g.W - 1));
+    r.h = (int)((r.m >> g.lw) & (g.H - 1));
+    r.d = (int)((r.m >> (g.lw + g.lh)) & (g.D - 1));
+    r.o = (int)(r.m >> (g.lw + g.lh + g.ld));
+    return r;
+}
+// tap t = (kd + 1) 9 + (kh + 1) 3 + (kw + 1) of the 27
+__device__ __forceinline__ void tap_coords(int t, int& kd, int& kh, int& kw) { kd = t / 9 - 1; kh = (t / 3) % 3 - 1; kw = t % 3 - 1; }
+// the A descriptor of a 27-tap launch starts this many bytes in front of the tensor: the largest negative tap shift
+__device__ __forceinline__ int tap_bias(int Hi, int Wi, int Cin) { return ((Hi + 1) * Wi + 1) * Cin * 2; }
+// the tap table: lane t holds the byte shift of tap t (+ bias, so that it is >= 0); one v_readlane per K unit fetches it
+__device__ __forceinline__ int tap_table(int lane, int Hi, int Wi, int Cin, int bias) {
+    int kd, kh, kw;
+    tap_coords(lane < 27 ? lane : 13, kd, kh, kw);
+    return ((kd * Hi + kh) * Wi + kw) * Cin * 2 + bias;
+}
+
+// NA: A pieces per lane and unit; piece j is slot p0 + pstride j of the tile.  UP_: nearest-neighbour up-sampling fused into the
+// gather (UP_HW / UP_DHW): the source of tap k along an up-sampled axis is (x + k) >> 1, i.e. the centre source shifted by -1
+// (k = -1, x even), +1 (k = +1, x odd) or 0 -- two per-lane byte shifts per axis, selected by the wave-uniform tap.  FOLD_
+// (k_conv_ws_fold): 12 folded taps per chunk, the tile's rows in (parity class, d, hi, wi) order, the class's weight image in a.w2.
+// PRECONDITION of the walk: a workgroup's K range is never empty (ks_begin < ks_end).  start() prepares unit ks_begin and k_conv_lean,
+// conv_ws_tile and k_conv_ws3 stage and multiply it without asking; only k_conv_kw's streams test for an empty range.  The automatic
+// split rules keep >= 5 units per part; an explicit es_conv_args.splitk above the number of cut units (nks0 / 3 for 27 taps, else
+// nks0, plus the skip's chunks) is still passed through by the host (caller_split, es_conv_route.hip) and breaks it.
+template <int NA, bool UP_, bool FOLD_ = false>
+struct ConvGather {
+    static_assert(!FOLD_ || UP_, "the folded taps are those of a nearest-up conv");
+    static constexpr unsigned OOB = 0x80000000u;             // >= num_records of both descriptors: the lane's 16 B arrive as zeros
+    ConvRow row[NA];
+    unsigned voff[NA], msk[NA];
+    int upm[3 * NA], upp[3 * NA];                // UP_: byte shift of tap -1 / +1 along (d, h, w) for this lane's row, [3 j + axis]
+    int dtab;                                    // the tap table of this phase
+    __amdgpu_buffer_rsrc_t rA, rB;               // this phase's activations (minus tap_bias) and this column tile's weight image
+                                                 // (the kernels pass them as (__amdgpu_buffer_rsrc_t)gth.rA: with a type-dependent argument the
+                                                 //  host pass checks the LDS-DMA builtin at instantiation, without the device's 16-byte feature)
+    unsigned sA, sbit;                           // per-unit scalars: soffset of the A pieces, the tap's bit in msk
+    int ukd, ukh, ukw;                           // UP_: tap coordinates of the unit
+    // The wave-uniform members stand LAST, and stay there.  At the switch to the skip phase st_c, st_boff and the per-lane dtab all become
+    // the constant 0; the compiler materialises one register per constant and block, for the first loop-carried value that takes it, and
+    // with the per-lane members behind the uniform ones that was a VGPR: st_c and st_boff followed it there, and every LDS-DMA load of
+    // the UP_ instantiations sat in a waterfall loop over its "per-lane" soffset (s_cbranch_execnz 2 -> 18 in k_conv_ws<256, 8, 4, true>;
+    // tools/kernel_asm_diff.py --table counts them, profiles/conv_gather_notes.md has the story).
+    int by, lane, nks0, fold_cls;
+    // K-step generator state: phase (1 = the skip), tap, channel chunk, their counts, byte offset of the B block
+    int st_phase, st_tap, st_c, st_ntap, st_kch;
+    unsigned st_boff;
+
+    __device__ __forceinline__ void rows(const ConvGeom& g, long m0, long M, int p0, int pstride) {
+        fold_cls = FOLD_ ? (int)((m0 >> (g.lw + g.lh + g.ld - 2)) & 3) : 0;       // (the whole tile is one class)
+#pragma unroll
+        for (int j = 0; j < NA; ++j) {
+            row[j] = conv_row_of(g, m0, M, p0 + pstride * j);
+            if constexpr (FOLD_) {
+                row[j].w = 2 * (int)(row[j].m & (g.Wi - 1)) + (fold_cls & 1);
+                row[j].h = 2 * (int)((row[j].m >> (g.lw - 1)) & (g.Hi - 1)) + (fold_cls >> 1);
+                row[j].d = (int)((row[j].m >> (g.lw + g.lh - 2)) & (g.D - 1));
+            }
+        }
+    }
+    __device__ __forceinline__ void set_phase(const es_conv_args& a, const ConvGeom& g) {
+        const _Float16* Wg = (const _Float16*)(st_phase ? a.w2 : a.w);
+        const long nks_ph = st_phase ? (long)(a.Cin2 >> 5) : (long)nks0;
+        if constexpr (FOLD_) Wg = (const _Float16*)a.w2 + ((long)fold_cls * ((a.N + BN - 1) / BN) * nks0) * (BNP * BK);      // the class's image
+        rB = __builtin_amdgcn_make_buffer_rsrc((void*)(Wg + ((long)by * nks_ph) * (BNP * BK)), (short)0, (int)OOB, 0x00020000);
+        const _Float16* Ag = (const _Float16*)(st_phase ? a.a2 : a.a);
+        const int Cin = st_phase ? a.Cin2 : a.Cin;
+        // DOWN_DHW_P01 (VQ-VAE encoder Downsample: far-face padding only): the tap centre is 2o + 1 instead of 2o; tap_mask27 around
+        // that centre drops exactly the +1 taps of the last output voxel of an axis, and the largest negative tap shift is unchanged
+        const int p01 = (!st_phase && a.mode == ES_CONV_DOWN_DHW_P01) ? 1 : 0;
+        const bool down = !st_phase && (a.mode == ES_CONV_DOWN_HW || a.mode == ES_CONV_DOWN_DHW || p01);
+        const bool downd = !st_phase && (a.mode == ES_CONV_DOWN_DHW || p01);
+        const int Dsrc = downd ? 2 * g.D : g.D;
+        const int Hi = st_phase ? g.H : g.Hi, Wi = st_phase ? g.W : g.Wi;
+        const int ntap = st_phase ? 1 : a.taps;
+        const bool updhw = UP_ && a.mode == ES_CONV_UP_DHW;
+        const int Di = updhw ? g.D / 2 : g.D;
+        const int bias = ntap == 27 ? tap_bias(Hi, Wi, Cin) : 0;
+        rA = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)Ag - bias), (short)0, (int)OOB, 0x00020000);
+        dtab = ntap == 27 ? tap_table(lane, Hi, Wi, Cin, bias) : 0;
+        if (UP_) {                               // h, w (and d) shifts are per lane
+            int kd, kh, kw;
+            tap_coords(lane < 27 ? lane : 13, kd, kh, kw);
+            dtab = ntap == 27 ? (updhw ? 0 : kd * Hi * Wi * Cin * 2) + bias : 0;
+        }
+#pragma unroll
+        for (int j = 0; j < NA; ++j) {
+            const ConvRow& r = row[j];
+            const int ch = down ? 2 * r.h + p01 : r.h;
+            const int cw = down ? 2 * r.w + p01 : r.w;
+            const int cd = downd ? 2 * r.d + p01 : r.d;
+            voff[j] = (unsigned)(((((long)r.o * Dsrc + cd) * Hi + ch) * Wi + cw) * Cin * 2 + r.lc * 16);
+            if (UP_) {
+                const int sd = updhw ? r.d >> 1 : r.d;
+                voff[j] = (unsigned)(((((long)r.o * Di + sd) * Hi + (r.h >> 1)) * Wi + (r.w >> 1)) * Cin * 2 + r.lc * 16);
+                const int SD = Hi * Wi * Cin * 2, SH = Wi * Cin * 2, SW = Cin * 2;
+                upm[3 * j + 0] = (updhw && !(r.d & 1)) ? -SD : 0; upp[3 * j + 0] = (updhw && (r.d & 1)) ? SD : 0;
+                upm[3 * j + 1] = !(r.h & 1) ? -SH : 0;            upp[3 * j + 1] = (r.h & 1) ? SH : 0;
+                upm[3 * j + 2] = !(r.w & 1) ? -SW : 0;            upp[3 * j + 2] = (r.w & 1) ? SW : 0;
+            }
+            unsigned m = 0;
+            if (ntap == 1) {
+                m = r.ok ? 1u : 0u;
+            } else {
+                m = r.ok ? tap_mask27(cd, Dsrc, ch, UP_ ? g.H : Hi, cw, UP_ ? g.W : Wi) : 0u;
+            }
+            msk[j] = m;
+        }
+    }
+    // the walk starts at K unit ks_begin of column tile by_ (units: the main phase's chunks x taps, then the skip's chunks)
+    __device__ __forceinline__ void start(const es_conv_args& a, const ConvGeom& g, int by_, int lane_, int ks_begin) {
+        by = by_; lane = lane_;
+        const int kch0 = a.Cin >> 5, ntap0 = FOLD_ ? 12 : a.taps;
+        nks0 = ntap0 * kch0;
+        st_phase = ks_begin >= nks0 ? 1 : 0;
+        st_tap = st_phase ? 0 : ks_begin % ntap0;
+        st_c = st_phase ? (ks_begin - nks0) : (ks_begin / ntap0);               // chunk index (32 channels)
+        st_ntap = st_phase ? 1 : ntap0; st_kch = st_phase ? (a.Cin2 >> 5) : kch0;
+        st_boff = (unsigned)(st_phase ? (ks_begin - nks0) : ks_begin) * (unsigned)(BNP * BK * 2);      // weight images: 16 KiB per K unit
+        set_phase(a, g);
+    }
+    // the scalars of the unit about to be staged
+    __device__ __forceinline__ void prep() {
+        int tap27 = st_tap;
+        // folded tap (kd, jh, jw) of class (ph, pw) is addressed as tap (kd, jh - 1 + ph, jw - 1 + pw) of the 27
+        if constexpr (FOLD_) tap27 = (st_tap >> 2) * 9 + (((st_tap >> 1) & 1) + (fold_cls >> 1)) * 3 + (st_tap & 1) + (fold_cls & 1);
+        sA = (unsigned)__builtin_amdgcn_readlane(dtab, tap27) + (unsigned)st_c * 64u;
+        sbit = 1u << tap27;
+        ukd = ukh = ukw = 0;
+        if (UP_) tap_coords(tap27, ukd, ukh, ukw);
+    }
+    // voffset of A piece j of the prepared unit (soffset sA, descriptor rA); out of range = zero fill for halo and ragged rows
+    __device__ __forceinline__ unsigned a_voff(int j) const {
+        unsigned vs = voff[j];
+        if (UP_) {
+            // (both shifts are read before the wave-uniform tap selects one: a select between the two ADDRESSES keeps this object in scratch)
+            const int md = upm[3 * j + 0], pd = upp[3 * j + 0], mh = upm[3 * j + 1], ph = upp[3 * j + 1], mw = upm[3 * j + 2], pw = upp[3 * j + 2];
+            vs += (unsigned)(ukd < 0 ? md : ukd > 0 ? pd : 0);
+            vs += (unsigned)(ukh < 0 ? mh : ukh > 0 ? ph : 0);
+            vs += (unsigned)(ukw < 0 ? mw : ukw > 0 ? pw : 0);
+        }
+        return (msk[j] & sbit) ? vs : OOB;
+    }
+    // to the next unit: next tap, next chunk, then the skip phase
+    __device__ __forceinline__ void advance(const es_conv_args& a, const ConvGeom& g) {
+        st_boff += (unsigned)(BNP * BK * 2);
+        if (++st_tap == st_ntap) {
+            st_tap = 0;
+            if (++st_c == st_kch && !st_phase && a.a2) {
+                st_phase = 1; st_c = 0; st_ntap = 1; st_kch = a.Cin2 >> 5; st_boff = 0;
+                set_phase(a, g);
+            }
+        }
+    }
+};
+
+// Fragment read address of lane (i16 = lane & 15, q = lane >> 4) in a swizzled [rows][64 B] LDS tile, for the 16-row MFMA tile that
+// starts at row0 (a multiple of 16): row bits 2..3 (the swizzle key) come from i16 only, so one per-lane base serves every
+// 16-row MFMA tile with an immediate offset
+__device__ __forceinline__ int frag_off(int row0, int lane) {
+    const int i16 = lane & 15, q = lane >> 4;
+    return (row0 + i16) * 64 + ((q ^ f_swz(i16)) << 4);
+}
+// voffset of a lane's 16 bytes of the B piece (1 KiB) that holds byte `at` of the 16 KiB weight block: bytes >= 224 rows x 64 B are the zero
+// rows that pad the weight tile to 256 -- never fetched, an out-of-range voffset makes them zero fills without L2 traffic (the
+// load count per wave stays the same; A/B on one box: 3x3x3 launches -0.5 ... -1 %, full step 47.9 -> 48.3 steps/s)
+__device__ __forceinline__ unsigned b_voff(unsigned at, unsigned voffB) { return at >= (unsigned)(BN * BK * 2) ? 0x80000000u : voffB; }
+
 // Workgroup = NW_ waves as (NW_/2)(M) x 2(N); tile BM_ x 224:
 //   <256, 8> wave tile 64 x 112 (16^3 and 16x8x8 levels: A+B bytes per flop -32 % vs <128,4>)
 //   <128, 4> wave tile 64 x 112
@@ -885,9 +1077,11 @@ template <int N_> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s
 // ks+1 under the MFMAs of step ks, 4 tiles in flight), a 6-deep ring for lone workgroups, issuing a wave's DMA pieces
 // in one block staggered against its SIMD partner.
 // ---------------------------------------------------------------------------------------------
-// UP_: nearest-neighbour up-sampling fused into the gather (UP_HW / UP_DHW): the source of tap k along an up-sampled
-// axis is (x + k) >> 1, i.e. the centre source shifted by -1 (k = -1, x even), +1 (k = +1, x odd) or 0 -- two per-lane
-// byte shifts per axis, selected by the wave-uniform tap.
+// UP_: nearest-neighbour up-sampling fused into the gather (UP_HW / UP_DHW), as in ConvGather.
+// This kernel, the reference tile, KEEPS ITS OWN COPY of the gather (row decode, K walk, set_phase, stage_prep / stage_piece /
+// stage_advance): on ConvGather its UP_ instantiations took 4 to 11 more VGPRs than before (192 -> 203, 190 -> 201, 116 -> 120) and
+// spilled 4 SGPRs (profiles/conv_gather_notes.md); with its own text all six instantiations are the code they were.  A mode added to
+// ConvGather::set_phase is added here as well.
 template <int BM_, int NW_, bool UP_ = false>
 __global__ __launch_bounds__(64 * NW_, 2) void k_conv_lean(const es_conv_args a, const ConvGeom g, int ncdhw) {
     constexpr int NS = 3;
@@ -948,8 +1142,7 @@ __global__ __launch_bounds__(64 * NW_, 2) void k_conv_lean(const es_conv_args a,
         rB = __builtin_amdgcn_make_buffer_rsrc((void*)(Wg + ((long)by * nks_ph) * (BNP * BK)), (short)0, (int)OOB, 0x00020000);
         const _Float16* Ag = (const _Float16*)(st_phase ? a.a2 : a.a);
         const int Cin = st_phase ? a.Cin2 : a.Cin;
-        // DOWN_DHW_P01 (VQ-VAE encoder Downsample: far-face padding only): the tap centre is 2o + 1 instead of 2o; tap_mask27 around
-        // that centre drops exactly the +1 taps of the last output voxel of an axis, and the largest negative tap shift is unchanged
+        // (DOWN_DHW_P01: explained at ConvGather::set_phase)
         const int p01 = (!st_phase && a.mode == ES_CONV_DOWN_DHW_P01) ? 1 : 0;
         const bool down = !st_phase && (a.mode == ES_CONV_DOWN_HW || a.mode == ES_CONV_DOWN_DHW || p01);
         const bool downd = !st_phase && (a.mode == ES_CONV_DOWN_DHW || p01);
@@ -1127,8 +1320,7 @@ __global__ __launch_bounds__(256) void k_linear_deep(const es_conv_args a, const
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_ptr)dst, 16, (int)voffA, (int)((unsigned)ks * 64u), 0, 0);
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
-            const unsigned vB = (unsigned)tid * 16u + (unsigned)j * (NT * 16) >= (unsigned)(BN * BK * 2) ? OOB : (unsigned)tid * 16u;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_ptr)(dst + A_BYTES + j * (NT * 16)), 16, (int)vB,
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_ptr)(dst + A_BYTES + j * (NT * 16)), 16, (int)b_voff((unsigned)tid * 16u + (unsigned)j * (NT * 16), (unsigned)tid * 16u),
                                                      (int)((unsigned)ks * (unsigned)B_BYTES + (unsigned)j * (NT * 16)), 0, 0);
         }
     };
@@ -1137,9 +1329,7 @@ __global__ __launch_bounds__(256) void k_linear_deep(const es_conv_args a, const
     for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int j = 0; j < 7; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-    const int i16 = lane & 15, q = lane >> 4;
-    const int fragA = (wm * WROWS + i16) * 64 + ((q ^ f_swz(i16)) << 4);
-    const int fragB = A_BYTES + (wn * 112 + i16) * 64 + ((q ^ f_swz(i16)) << 4);
+    const int fragA = frag_off(wm * WROWS, lane), fragB = A_BYTES + frag_off(wn * 112, lane);
     int issued = 0;
     for (; issued < NS - 1 && issued < nloc; ++issued) stage(issued, issued);
     int slot = 0;
@@ -1243,138 +1433,32 @@ __device__ __forceinline__ void conv_ws_tile(const es_conv_args& a, const ConvGe
     constexpr int APIECES = BM_ / 16, BPIECES = BNP / 16;          // 1 KiB pieces per unit
     constexpr int NA = APIECES / NP_, NB = BPIECES / NP_, NLOAD = NA + NB;        // per producer wave per unit
     static_assert(APIECES % NP_ == 0 && BPIECES % NP_ == 0, "pieces must divide over the producer waves");
-    constexpr unsigned OOB = 0x80000000u;
     typedef __attribute__((address_space(3))) void* lds_ptr;
     (void)stamp;
     const long m0 = (long)bx * BM_;
     const int n0 = by * BN;
-    const int kch0 = a.Cin >> 5;
-    const int ntap0 = FOLD_ ? 12 : a.taps;
-    const int nks0 = ntap0 * kch0;
     const int nloc = ks_end - ks_begin;                           // K units of this workgroup
     const int nstage = (nloc + UPS_ - 1) / UPS_;
-    static_assert(!FOLD_ || UP_, "the folded taps are those of a nearest-up conv");
-    const int fold_cls = FOLD_ ? (int)((m0 >> (g.lw + g.lh + g.ld - 2)) & 3) : 0;       // (the whole tile is one class)
-    const int fold_ph = fold_cls >> 1, fold_pw = fold_cls & 1;
     if (wave >= NC_) {
         // =============================== producer ===============================
         const int pw = wave - NC_;
-        int a_lc[NA], a_o[NA], a_d[NA], a_h[NA], a_w[NA];
-        bool a_ok[NA];
-#pragma unroll
-        for (int j = 0; j < NA; ++j) {
-            const int p = (pw + NP_ * j) * 64 + lane;    // 16-B slot of the A tile: row = p >> 2, physical chunk = p & 3
-            const int row = p >> 2;
-            a_lc[j] = (p & 3) ^ f_swz(row);
-            const long m = m0 + row;
-            a_ok[j] = m < M;
-            const long mm = a_ok[j] ? m : 0;
-            a_w[j] = (int)(mm & (g.W - 1));
-            a_h[j] = (int)((mm >> g.lw) & (g.H - 1));
-            a_d[j] = (int)((mm >> (g.lw + g.lh)) & (g.D - 1));
-            a_o[j] = (int)(mm >> (g.lw + g.lh + g.ld));
-            if constexpr (FOLD_) {
-                a_w[j] = 2 * (int)(mm & (g.Wi - 1)) + fold_pw;
-                a_h[j] = 2 * (int)((mm >> (g.lw - 1)) & (g.Hi - 1)) + fold_ph;
-                a_d[j] = (int)((mm >> (g.lw + g.lh - 2)) & (g.D - 1));
-            }
-        }
-        int st_phase = ks_begin >= nks0 ? 1 : 0;
-        int st_tap = st_phase ? 0 : ks_begin % ntap0;
-        int st_c = st_phase ? (ks_begin - nks0) : (ks_begin / ntap0);
-        int st_ntap = st_phase ? 1 : ntap0, st_kch = st_phase ? (a.Cin2 >> 5) : kch0;
-        unsigned st_boff = (unsigned)(st_phase ? (ks_begin - nks0) : ks_begin) * (unsigned)B_BYTES;
-        unsigned voff[NA], msk[NA];
-        int upm[NA][3], upp[NA][3];
-        int dtab = 0;
-        __amdgpu_buffer_rsrc_t rA, rB;
-        auto set_phase = [&]() __attribute__((always_inline)) {
-            const _Float16* Wg = (const _Float16*)(st_phase ? a.w2 : a.w);
-            const long nks_ph = st_phase ? (long)(a.Cin2 >> 5) : (long)nks0;
-            if constexpr (FOLD_) Wg = (const _Float16*)a.w2 + ((long)fold_cls * ((a.N + BN - 1) / BN) * nks0) * (BNP * BK);      // the class's image
-            rB = __builtin_amdgcn_make_buffer_rsrc((void*)(Wg + ((long)by * nks_ph) * (BNP * BK)), (short)0, (int)OOB, 0x00020000);
-            const _Float16* Ag = (const _Float16*)(st_phase ? a.a2 : a.a);
-            const int Cin = st_phase ? a.Cin2 : a.Cin;
-            // DOWN_DHW_P01 (VQ-VAE encoder Downsample: far-face padding only): the tap centre is 2o + 1 instead of 2o; tap_mask27 around
-            // that centre drops exactly the +1 taps of the last output voxel of an axis, and the largest negative tap shift is unchanged
-            const int p01 = (!st_phase && a.mode == ES_CONV_DOWN_DHW_P01) ? 1 : 0;
-            const bool down = !st_phase && (a.mode == ES_CONV_DOWN_HW || a.mode == ES_CONV_DOWN_DHW || p01);
-            const bool downd = !st_phase && (a.mode == ES_CONV_DOWN_DHW || p01);
-            const int Dsrc = downd ? 2 * g.D : g.D;
-            const int Hi = st_phase ? g.H : g.Hi, Wi = st_phase ? g.W : g.Wi;
-            const int ntap = st_phase ? 1 : a.taps;
-            const bool updhw = UP_ && a.mode == ES_CONV_UP_DHW;
-            const int Di = updhw ? g.D / 2 : g.D;
-            const int bias = ntap == 27 ? ((Hi + 1) * Wi + 1) * Cin * 2 : 0;
-            rA = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)Ag - bias), (short)0, (int)OOB, 0x00020000);
-            {
-                const int t = lane < 27 ? lane : 13;
-                const int kd = t / 9 - 1, kh = (t / 3) % 3 - 1, kw = t % 3 - 1;
-                dtab = ntap == 27 ? ((kd * Hi + kh) * Wi + kw) * Cin * 2 + bias : 0;
-                if (UP_) dtab = ntap == 27 ? (updhw ? 0 : kd * Hi * Wi * Cin * 2) + bias : 0;
-            }
-#pragma unroll
-            for (int j = 0; j < NA; ++j) {
-                const int ch = down ? 2 * a_h[j] + p01 : a_h[j];
-                const int cw = down ? 2 * a_w[j] + p01 : a_w[j];
-                const int cd = downd ? 2 * a_d[j] + p01 : a_d[j];
-                voff[j] = (unsigned)(((((long)a_o[j] * Dsrc + cd) * Hi + ch) * Wi + cw) * Cin * 2 + a_lc[j] * 16);
-                if (UP_) {
-                    const int sd = updhw ? a_d[j] >> 1 : a_d[j];
-                    voff[j] = (unsigned)(((((long)a_o[j] * Di + sd) * Hi + (a_h[j] >> 1)) * Wi + (a_w[j] >> 1)) * Cin * 2 + a_lc[j] * 16);
-                    const int SD = Hi * Wi * Cin * 2, SH = Wi * Cin * 2, SW = Cin * 2;
-                    upm[j][0] = (updhw && !(a_d[j] & 1)) ? -SD : 0; upp[j][0] = (updhw && (a_d[j] & 1)) ? SD : 0;
-                    upm[j][1] = !(a_h[j] & 1) ? -SH : 0;            upp[j][1] = (a_h[j] & 1) ? SH : 0;
-                    upm[j][2] = !(a_w[j] & 1) ? -SW : 0;            upp[j][2] = (a_w[j] & 1) ? SW : 0;
-                }
-                unsigned m = 0;
-                if (ntap == 1) {
-                    m = a_ok[j] ? 1u : 0u;
-                } else {
-                    m = a_ok[j] ? tap_mask27(cd, Dsrc, ch, UP_ ? g.H : Hi, cw, UP_ ? g.W : Wi) : 0u;
-                }
-                msk[j] = m;
-            }
-        };
-        set_phase();
+        ConvGather<NA, UP_, FOLD_> gth;
+        gth.rows(g, m0, M, pw * 64 + lane, NP_ * 64);        // A piece j of a producer wave: 1 KiB piece pw + NP_ j
+        gth.start(a, g, by, lane, ks_begin);
         ES_STAMP_AT(1);
         const unsigned voffB = (unsigned)lane * 16u;
         auto issue_unit = [&](char* dst) __attribute__((always_inline)) {        // dst: LDS base of the unit (A tile, then B tile)
-            int tap27 = st_tap;
-            if constexpr (FOLD_) tap27 = (st_tap >> 2) * 9 + (((st_tap >> 1) & 1) + fold_ph) * 3 + (st_tap & 1) + fold_pw;
-            const unsigned sA = (unsigned)__builtin_amdgcn_readlane(dtab, tap27) + (unsigned)st_c * 64u;
-            const unsigned sbit = 1u << tap27;
-            int ukd = 0, ukh = 0, ukw = 0;
-            if (UP_) { ukd = tap27 / 9 - 1; ukh = (tap27 / 3) % 3 - 1; ukw = tap27 % 3 - 1; }
+            gth.prep();
 #pragma unroll
-            for (int j = 0; j < NA; ++j) {
-                unsigned vs = voff[j];
-                if (UP_) {
-                    vs += (unsigned)(ukd < 0 ? upm[j][0] : ukd > 0 ? upp[j][0] : 0);
-                    vs += (unsigned)(ukh < 0 ? upm[j][1] : ukh > 0 ? upp[j][1] : 0);
-                    vs += (unsigned)(ukw < 0 ? upm[j][2] : ukw > 0 ? upp[j][2] : 0);
-                }
-                const unsigned vo = (msk[j] & sbit) ? vs : OOB;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_ptr)(dst + (pw + NP_ * j) * 1024), 16, (int)vo, (int)sA, 0, 0);
-            }
+            for (int j = 0; j < NA; ++j)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds((__amdgpu_buffer_rsrc_t)gth.rA, (lds_ptr)(dst + (pw + NP_ * j) * 1024), 16, (int)gth.a_voff(j), (int)gth.sA, 0, 0);
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
-                const int q = pw + NP_ * j;
-                // pieces 14, 15 are the 32 zero rows that pad the 224-column weight tile to 256: never read by the consumers --
-                // an out-of-range voffset makes them zero fills without L2 traffic (the load count per wave stays the same; A/B on one
-                // box: 3x3x3 launches -0.5 ... -1 %, full step 47.9 -> 48.3 steps/s)
-                const unsigned vB = q * 16 >= BN ? OOB : voffB;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_ptr)(dst + A_BYTES + q * 1024), 16, (int)vB,
-                                                         (int)(st_boff + (unsigned)q * 1024u), 0, 0);
+                const int q = pw + NP_ * j;      // (pieces 14, 15 are the zero rows: never read by the consumers)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds((__amdgpu_buffer_rsrc_t)gth.rB, (lds_ptr)(dst + A_BYTES + q * 1024), 16, (int)b_voff(q * 1024, voffB),
+                                                         (int)(gth.st_boff + (unsigned)q * 1024u), 0, 0);
             }
-            st_boff += (unsigned)B_BYTES;
-            if (++st_tap == st_ntap) {
-                st_tap = 0;
-                if (++st_c == st_kch && !st_phase && a.a2) {
-                    st_phase = 1; st_c = 0; st_ntap = 1; st_kch = a.Cin2 >> 5; st_boff = 0;
-                    set_phase();
-                }
-            }
+            gth.advance(a, g);
         };
         int issued = 0;                          // K units issued so far
         auto issue_stage = [&](int st) __attribute__((always_inline)) {
@@ -1408,9 +1492,7 @@ __device__ __forceinline__ void conv_ws_tile(const es_conv_args& a, const ConvGe
     for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int j = 0; j < 7; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-    const int i16 = lane & 15, q = lane >> 4;
-    const int fragA = (wm * WROWS + i16) * 64 + ((q ^ f_swz(i16)) << 4);
-    const int fragB = A_BYTES + (wn * 112 + i16) * 64 + ((q ^ f_swz(i16)) << 4);
+    const int fragA = frag_off(wm * WROWS, lane), fragB = A_BYTES + frag_off(wn * 112, lane);
     h8 af[MI], bfr[7];
     {
         // Software pipeline WITHOUT a second fragment buffer (112 accumulators + 44 fragment registers is all the 168-register
@@ -1575,26 +1657,14 @@ __global__ __launch_bounds__(768, 3) void k_conv_ws3(const es_conv_args a, const
         unsigned voff[NA], msk[NA];
 #pragma unroll
         for (int j = 0; j < NA; ++j) {
-            const int p = (pw + NP_ * j) * 64 + lane;
-            const int row = p >> 2;
-            const int lc = (p & 3) ^ f_swz(row);
-            const long m = m0 + row;
-            const bool ok = m < M;
-            const long mm = ok ? m : 0;
-            const int w = (int)(mm & (g.W - 1)), h = (int)((mm >> g.lw) & (g.H - 1)), d = (int)((mm >> (g.lw + g.lh)) & (g.D - 1));
-            const int o = (int)(mm >> (g.lw + g.lh + g.ld));
-            voff[j] = (unsigned)(((((long)o * g.D + d) * g.H + h) * g.W + w) * a.Cin * 2 + lc * 16);
-            msk[j] = ok ? tap_mask27(d, g.D, h, g.H, w, g.W) : 0u;
+            const ConvRow r = conv_row_of(g, m0, M, (pw + NP_ * j) * 64 + lane);
+            voff[j] = (unsigned)(((((long)r.o * g.D + r.d) * g.H + r.h) * g.W + r.w) * a.Cin * 2 + r.lc * 16);
+            msk[j] = r.ok ? tap_mask27(r.d, g.D, r.h, g.H, r.w, g.W) : 0u;
         }
-        const int bias = ((g.H + 1) * g.W + 1) * a.Cin * 2;
+        const int bias = tap_bias(g.H, g.W, a.Cin);
         const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)a.a - bias), (short)0, (int)OOB, 0x00020000);
         const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)((const _Float16*)a.w + ((long)by * nks0) * (BNP * BK)), (short)0, (int)OOB, 0x00020000);
-        int dtab;
-        {
-            const int t = lane < 27 ? lane : 13;
-            const int kd = t / 9 - 1, kh = (t / 3) % 3 - 1, kw = t % 3 - 1;
-            dtab = ((kd * g.H + kh) * g.W + kw) * a.Cin * 2 + bias;
-        }
+        const int dtab = tap_table(lane, g.H, g.W, a.Cin, bias);
         int a_tap = ks_begin % 27, a_c = ks_begin / 27;               // first tap (kw = -1) and channel chunk of the next group to load
         unsigned b_off = (unsigned)ks_begin * (unsigned)B_BYTES;
         const unsigned voffB = (unsigned)lane * 16u;
@@ -1613,7 +1683,7 @@ __global__ __launch_bounds__(768, 3) void k_conv_ws3(const es_conv_args a, const
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
                 const int q = pw + NP_ * j;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_ptr)(dst + q * 1024), 16, (int)(q * 16 >= BN ? OOB : voffB), (int)(b_off + (unsigned)q * 1024u), 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_ptr)(dst + q * 1024), 16, (int)b_voff(q * 1024, voffB), (int)(b_off + (unsigned)q * 1024u), 0, 0);
             }
             b_off += (unsigned)B_BYTES;
         };
@@ -1641,9 +1711,8 @@ __global__ __launch_bounds__(768, 3) void k_conv_ws3(const es_conv_args a, const
     for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int j = 0; j < 7; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-    const int i16 = lane & 15, q = lane >> 4;
-    const int fragA = A_RING + (wm * 64 + i16) * 64 + ((q ^ f_swz(i16)) << 4);
-    const int fragB = (wn * 112 + i16) * 64 + ((q ^ f_swz(i16)) << 4);
+    const int i16 = lane & 15;
+    const int fragA = A_RING + frag_off(wm * 64, lane), fragB = frag_off(wn * 112, lane);
     const bool zl = (i16 & (g.W - 1)) == 0, zr = (i16 & (g.W - 1)) == ((g.W - 1) & 15);      // first / last voxel of a W line
     // MFMA order: B column outer, A row inner -- one B fragment is live at a time (3 in a prefetch ring) instead of all 7, which pays for
     // the 4 shifted A fragments of the kw = -1 / +1 units inside the 168-register budget (112 accumulators + 16 centre + 16 shifted +
@@ -1726,26 +1795,15 @@ __global__ __launch_bounds__(64 * (KS_ * NCH_ + 8), 3) void k_conv_kw(const es_c
     constexpr int JA = APIECES / NPW, JMAX = (NPIECE + NPW - 1) / NPW;              // pieces j < JA of a producer wave are A pieces
     static_assert(APIECES % NPW == 0, "A pieces must divide over a stream's producer waves");
     constexpr int PART_FLOATS = 112 * 64;                                         // one consumer wave's accumulators, [register][lane]
-    constexpr unsigned OOB = 0x80000000u;
     typedef __attribute__((address_space(3))) void* lds_ptr;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const long M = (long)g.O * g.D * g.H * g.W;
-    // tile mapping: XCD-contiguous ranges of logical ids, row tiles fastest (neighbours share the weight slab and the halo)
-    int bx, byh, bz;
-    {
-        const int gx = gridDim.x, gy = gridDim.y;
-        const int nwg = gx * gy * (int)gridDim.z;
-        const int orig = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
-        const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-        const int L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-        const int per_z = gx * gy;
-        bz = L / per_z;
-        const int t = L - bz * per_z;
-        bx = t % gx;
-        byh = t / gx;
-    }
+    const int gx = gridDim.x, gy = gridDim.y;
+    int t, bz;
+    grid_tile_id(gx, gy, t, bz);
+    const int bx = t % gx, byh = t / gx;         // row tiles fastest (neighbours share the weight slab and the halo)
     const int by = NCH_ == 2 ? byh : (byh >> 1), half0 = NCH_ == 2 ? 0 : (byh & 1);      // 224-column weight tile, first 112-column half
     const int S = gridDim.z;
     const long m0 = (long)bx * BM_;
@@ -1766,107 +1824,23 @@ __global__ __launch_bounds__(64 * (KS_ * NCH_ + 8), 3) void k_conv_kw(const es_c
         split_range(nks0, a.a2 ? (a.Cin2 >> 5) : 0, a.taps, bz * KS_ + strm, S * KS_, ks_begin, ks_end);
         const int nloc = ks_end - ks_begin;
         const int npc = (NPIECE - sub + NPW - 1) / NPW;          // pieces of this wave per unit (JMAX or JMAX - 1)
-        int a_lc[JA], a_o[JA], a_d[JA], a_h[JA], a_w[JA];
-        bool a_ok[JA];
-#pragma unroll
-        for (int j = 0; j < JA; ++j) {
-            const int p = (sub + NPW * j) * 64 + lane;   // 16-B slot of the A tile: row = p >> 2, physical chunk = p & 3
-            const int row = p >> 2;
-            a_lc[j] = (p & 3) ^ f_swz(row);
-            const long m = m0 + row;
-            a_ok[j] = m < M;
-            const long mm = a_ok[j] ? m : 0;
-            a_w[j] = (int)(mm & (g.W - 1));
-            a_h[j] = (int)((mm >> g.lw) & (g.H - 1));
-            a_d[j] = (int)((mm >> (g.lw + g.lh)) & (g.D - 1));
-            a_o[j] = (int)(mm >> (g.lw + g.lh + g.ld));
-        }
-        int st_phase = ks_begin >= nks0 ? 1 : 0;
-        int st_tap = st_phase ? 0 : ks_begin % a.taps;
-        int st_c = st_phase ? (ks_begin - nks0) : (ks_begin / a.taps);
-        int st_ntap = st_phase ? 1 : a.taps, st_kch = st_phase ? (a.Cin2 >> 5) : kch0;
-        unsigned st_boff = (unsigned)(st_phase ? (ks_begin - nks0) : ks_begin) * (unsigned)(BNP * BK * 2);      // weight images: 16 KiB per K step
-        unsigned voff[JA], msk[JA];
-        int upm[JA][3], upp[JA][3];
-        int dtab = 0;
-        __amdgpu_buffer_rsrc_t rA, rB;
-        auto set_phase = [&]() __attribute__((always_inline)) {
-            const _Float16* Wg = (const _Float16*)(st_phase ? a.w2 : a.w);
-            const long nks_ph = st_phase ? (long)(a.Cin2 >> 5) : (long)nks0;
-            rB = __builtin_amdgcn_make_buffer_rsrc((void*)(Wg + ((long)by * nks_ph) * (BNP * BK)), (short)0, (int)OOB, 0x00020000);
-            const _Float16* Ag = (const _Float16*)(st_phase ? a.a2 : a.a);
-            const int Cin = st_phase ? a.Cin2 : a.Cin;
-            // DOWN_DHW_P01 (VQ-VAE encoder Downsample: far-face padding only): the tap centre is 2o + 1 instead of 2o; tap_mask27 around
-            // that centre drops exactly the +1 taps of the last output voxel of an axis, and the largest negative tap shift is unchanged
-            const int p01 = (!st_phase && a.mode == ES_CONV_DOWN_DHW_P01) ? 1 : 0;
-            const bool down = !st_phase && (a.mode == ES_CONV_DOWN_HW || a.mode == ES_CONV_DOWN_DHW || p01);
-            const bool downd = !st_phase && (a.mode == ES_CONV_DOWN_DHW || p01);
-            const int Dsrc = downd ? 2 * g.D : g.D;
-            const int Hi = st_phase ? g.H : g.Hi, Wi = st_phase ? g.W : g.Wi;
-            const int ntap = st_phase ? 1 : a.taps;
-            const bool updhw = UP_ && a.mode == ES_CONV_UP_DHW;
-            const int Di = updhw ? g.D / 2 : g.D;
-            const int bias = ntap == 27 ? ((Hi + 1) * Wi + 1) * Cin * 2 : 0;
-            rA = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)Ag - bias), (short)0, (int)OOB, 0x00020000);
-            {
-                const int t = lane < 27 ? lane : 13;
-                const int kd = t / 9 - 1, kh = (t / 3) % 3 - 1, kw = t % 3 - 1;
-                dtab = ntap == 27 ? ((kd * Hi + kh) * Wi + kw) * Cin * 2 + bias : 0;
-                if (UP_) dtab = ntap == 27 ? (updhw ? 0 : kd * Hi * Wi * Cin * 2) + bias : 0;
-            }
-#pragma unroll
-            for (int j = 0; j < JA; ++j) {
-                const int ch = down ? 2 * a_h[j] + p01 : a_h[j];
-                const int cw = down ? 2 * a_w[j] + p01 : a_w[j];
-                const int cd = downd ? 2 * a_d[j] + p01 : a_d[j];
-                voff[j] = (unsigned)(((((long)a_o[j] * Dsrc + cd) * Hi + ch) * Wi + cw) * Cin * 2 + a_lc[j] * 16);
-                if (UP_) {
-                    const int sd = updhw ? a_d[j] >> 1 : a_d[j];
-                    voff[j] = (unsigned)(((((long)a_o[j] * Di + sd) * Hi + (a_h[j] >> 1)) * Wi + (a_w[j] >> 1)) * Cin * 2 + a_lc[j] * 16);
-                    const int SD = Hi * Wi * Cin * 2, SH = Wi * Cin * 2, SW = Cin * 2;
-                    upm[j][0] = (updhw && !(a_d[j] & 1)) ? -SD : 0; upp[j][0] = (updhw && (a_d[j] & 1)) ? SD : 0;
-                    upm[j][1] = !(a_h[j] & 1) ? -SH : 0;            upp[j][1] = (a_h[j] & 1) ? SH : 0;
-                    upm[j][2] = !(a_w[j] & 1) ? -SW : 0;            upp[j][2] = (a_w[j] & 1) ? SW : 0;
-                }
-                unsigned m = 0;
-                if (ntap == 1) m = a_ok[j] ? 1u : 0u;
-                else m = a_ok[j] ? tap_mask27(cd, Dsrc, ch, UP_ ? g.H : Hi, cw, UP_ ? g.W : Wi) : 0u;
-                msk[j] = m;
-            }
-        };
-        set_phase();
+        ConvGather<JA, UP_> gth;
+        gth.rows(g, m0, M, sub * 64 + lane, NPW * 64);       // A piece j of a producer wave: 1 KiB piece sub + NPW j of its stream's tile
+        gth.start(a, g, by, lane, ks_begin);
         const unsigned voffB = (unsigned)lane * 16u;
         auto issue_unit = [&](char* dst) __attribute__((always_inline)) {        // dst: LDS base of this stream's unit (A tile, then B tile)
-            const unsigned sA = (unsigned)__builtin_amdgcn_readlane(dtab, st_tap) + (unsigned)st_c * 64u;
-            const unsigned sbit = 1u << st_tap;
-            int ukd = 0, ukh = 0, ukw = 0;
-            if (UP_) { ukd = st_tap / 9 - 1; ukh = (st_tap / 3) % 3 - 1; ukw = st_tap % 3 - 1; }
+            gth.prep();
 #pragma unroll
-            for (int j = 0; j < JA; ++j) {
-                unsigned vs = voff[j];
-                if (UP_) {
-                    vs += (unsigned)(ukd < 0 ? upm[j][0] : ukd > 0 ? upp[j][0] : 0);
-                    vs += (unsigned)(ukh < 0 ? upm[j][1] : ukh > 0 ? upp[j][1] : 0);
-                    vs += (unsigned)(ukw < 0 ? upm[j][2] : ukw > 0 ? upp[j][2] : 0);
-                }
-                const unsigned vo = (msk[j] & sbit) ? vs : OOB;
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_ptr)(dst + (sub + NPW * j) * 1024), 16, (int)vo, (int)sA, 0, 0);
-            }
+            for (int j = 0; j < JA; ++j)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds((__amdgpu_buffer_rsrc_t)gth.rA, (lds_ptr)(dst + (sub + NPW * j) * 1024), 16, (int)gth.a_voff(j), (int)gth.sA, 0, 0);
 #pragma unroll
             for (int j = JA; j < JMAX; ++j) {
                 const int qb = sub + NPW * j - APIECES;                           // 1 KiB piece (16 weight rows) of this tile's NCH_ x 7
                 if (j < JMAX - 1 || qb < BPIECES)                                 // (wave-uniform: the last piece exists for the first waves only)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_ptr)(dst + A_BYTES + qb * 1024), 16, (int)voffB,
-                                                             (int)(st_boff + (unsigned)(half0 * 7 + qb) * 1024u), 0, 0);
+                    __builtin_amdgcn_raw_ptr_buffer_load_lds((__amdgpu_buffer_rsrc_t)gth.rB, (lds_ptr)(dst + A_BYTES + qb * 1024), 16, (int)voffB,
+                                                             (int)(gth.st_boff + (unsigned)(half0 * 7 + qb) * 1024u), 0, 0);
             }
-            st_boff += (unsigned)(BNP * BK * 2);
-            if (++st_tap == st_ntap) {
-                st_tap = 0;
-                if (++st_c == st_kch && !st_phase && a.a2) {
-                    st_phase = 1; st_c = 0; st_ntap = 1; st_kch = a.Cin2 >> 5; st_boff = 0;
-                    set_phase();
-                }
-            }
+            gth.advance(a, g);
         };
         auto wait_own = [&](bool more) __attribute__((always_inline)) {           // the pieces of the oldest unit in flight have landed
             if (!more) wait_vmcnt<0>();
@@ -1899,9 +1873,7 @@ __global__ __launch_bounds__(64 * (KS_ * NCH_ + 8), 3) void k_conv_kw(const es_c
     for (int i = 0; i < MI; ++i)
 #pragma unroll
         for (int j = 0; j < 7; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-    const int i16 = lane & 15, q = lane >> 4;
-    const int fragA = strm * UNIT_BYTES + i16 * 64 + ((q ^ f_swz(i16)) << 4);
-    const int fragB = strm * UNIT_BYTES + A_BYTES + hh * (112 * 64) + i16 * 64 + ((q ^ f_swz(i16)) << 4);
+    const int fragA = strm * UNIT_BYTES + frag_off(0, lane), fragB = strm * UNIT_BYTES + A_BYTES + frag_off(hh * 112, lane);
     {
         h8 af[MI], bfr[7];
         int slot = 0, done = 0;                                                 // barriers passed so far
@@ -2001,22 +1973,8 @@ __global__ __launch_bounds__(768, 3) void k_linear_ws(const es_conv_args a, cons
     unsigned long long* stamp = g_stamp_buf ? g_stamp_buf + ((size_t)(blockIdx.x + gridDim.x * blockIdx.y) * (NC_ + NP_) + wave) * 8 : nullptr;
 #endif
     ES_STAMP_AT(0);
-    // tile mapping as conv_tile_of (XCD-contiguous ranges, column GROUPS fastest inside ~3 MiB weight panels)
-    int bx, byg;
-    {
-        const int gx = gridDim.x, gy = gridDim.y, nwg = gx * gy;
-        const int orig = blockIdx.x + gx * blockIdx.y;
-        const int xcd = orig & 7, q = nwg >> 3, r = nwg & 7;
-        const int L = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-        const long slab = (long)a.Cin * BN * 2 * ncb;
-        int npanel = (int)(((long)gy * slab + (3L << 20) - 1) / (3L << 20));
-        npanel = npanel < 1 ? 1 : (npanel > gy ? gy : npanel);
-        const int Pw = (gy + npanel - 1) / npanel, full = gx * Pw;
-        const int p = L / full, rr = L - p * full;
-        const int w = (gy - p * Pw) < Pw ? (gy - p * Pw) : Pw;
-        bx = rr / w;
-        byg = p * Pw + (rr - bx * w);
-    }
+    int bx, byg;                                 // column GROUPS fastest inside the weight panels (a group's slab = ncb column tiles)
+    panel_tile_of(xcd_logical_id(gridDim.x * gridDim.y, blockIdx.x + gridDim.x * blockIdx.y), gridDim.x, gridDim.y, (long)a.Cin * BN * 2 * ncb, bx, byg);
     const long m0 = (long)bx * BM_;
     const int by0 = byg * ncb;
     const int kch = a.Cin >> 5;                  // K units per column tile
@@ -2047,8 +2005,7 @@ __global__ __launch_bounds__(768, 3) void k_linear_ws(const es_conv_args a, cons
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
                 const int q = pw + NP_ * j;
-                const unsigned vB = q * 16 >= BN ? OOB : voffB;          // the zero rows padding the weight tile: zero fill, no traffic
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_ptr)(dst + A_BYTES + q * 1024), 16, (int)vB, (int)(sB + (unsigned)q * 1024u), 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rB, (lds_ptr)(dst + A_BYTES + q * 1024), 16, (int)b_voff(q * 1024, voffB), (int)(sB + (unsigned)q * 1024u), 0, 0);
             }
             islot = islot == NS - 1 ? 0 : islot + 1;
             if (++c == kch) {                    // next column tile: same rows, next weight slab
@@ -2070,9 +2027,7 @@ __global__ __launch_bounds__(768, 3) void k_linear_ws(const es_conv_args a, cons
     }
     // =============================== consumer ===============================
     const int wm = wave >> 1, wn = wave & 1;
-    const int i16 = lane & 15, q = lane >> 4;
-    const int fragA = (wm * WROWS + i16) * 64 + ((q ^ f_swz(i16)) << 4);
-    const int fragB = A_BYTES + (wn * 112 + i16) * 64 + ((q ^ f_swz(i16)) << 4);
+    const int fragA = frag_off(wm * WROWS, lane), fragB = A_BYTES + frag_off(wn * 112, lane);
     int slot = 0;
     for (int cb = 0; cb < ncb; ++cb) {
         f4 acc[MI][7];
