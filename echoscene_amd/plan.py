@@ -927,10 +927,16 @@ def emit_gcn(b, gw, g, obj, Dobj, pred, Dp, out=None, want_pred=False, rider=Non
         # net2's second Linear and the predicate projection (it needs net1's predicate columns and the layer's predicates, nothing of
         # net2) are independent: ONE launch.  (Round 5: the projection sat on the pooling launch before; a fused group takes ONE kernel
         # family, the pooling is k_linear_rows', and a product must take the same route -- the same bits -- whatever it is fused with.)
+        # (with lanes the projection is a branch of its own: forked behind net1's second Linear, whose predicate columns it reads, and
+        #  joined before the next layer reads it.  It used to sit on lane 2 behind the join above with no fork and no join of its
+        #  own -- unordered against the producer of t2 and against the next layer's first product, tests/plan_footprint.py)
+        if need_newp:
+            b.fork(2)
         b.linear([seg(n1, pre_act=hip.ACT_RELU)], L['n2b'], O, dst, act=hip.ACT_RELU, res=proj, fuse_next=need_newp)
         if need_newp:
             newp = View(b.buf(T, Dp))
             b.linear([seg(pred, width=Dp)], L['projp'], T, newp, res=View(t2.t, col=H, ld=W2, width=Dp), lane=2)
+            b.join(2)
         elif not has_proj:
             newp = View(t2.t, col=H, ld=W2, width=Dp)
         b.ride(rider)

@@ -9,8 +9,9 @@ buffer is the tensor storage, kept alive by the plan (Builder.keep) or handed in
 contains the address; ordinals are given in order of first appearance.  Per buffer: byte size, the dtypes of the tensors on it,
 whether the plan claims it as scratch.  Per plan also weight_bytes, flops, the tags and what the step hands back to its caller.
 
-The file in this commit was recorded from the planner as it was BEFORE its refactoring; regenerate it only when a change of the
-plans is intended, and say so in the commit.
+The file was recorded from the planner as it was BEFORE its refactoring; regenerate it only when a change of the plans is intended,
+and say so in the commit.  (Regenerated once since: `tiny lanes` forks and joins the predicate projection of every GCN layer -- the
+race tests/test_plan_footprint_cpu.py found; the other 24 documents did not change.)
 
 usage: python tests/golden/make_vol_plans.py"""
 import bisect
@@ -177,13 +178,13 @@ def make_builder(dev, precision='fp16', o_hint=0, up_fold=False, shard_block=Non
     return b
 
 
-def unet_weights(width, ctx, concat, mp, precision):
-    """packed UNet3DWeights, once per process and network (the full-width one takes seconds on the host)"""
+def unet_weights(width, ctx, concat, mp, precision, dev='cpu'):
+    """packed UNet3DWeights, once per process, network and device (the full-width one takes seconds on the host)"""
     from echoscene_amd import synth, config as escfg
     from echoscene_amd.model.unet import DiffusionUNet
     from echoscene_amd.plan_vol import UNet3DWeights
     from echoscene_amd.samplers import _cpu_sd
-    key = (width, ctx, concat, mp, precision)
+    key = (width, ctx, concat, mp, precision, str(dev))
     if key not in _weights:
         p = escfg.shape_unet_params(width, concat=concat, mp=mp)
         if not concat:
@@ -191,18 +192,21 @@ def unet_weights(width, ctx, concat, mp, precision):
         df = DiffusionUNet(p, conditioning_key='concat' if concat else 'crossattn')
         synth.seeded_fill_(df, prefix='vol_plans.%d.' % width)
         sd = {k[len('diffusion_net.'):]: v for k, v in _cpu_sd(df).items()}
-        _weights[key] = UNet3DWeights(sd, df.diffusion_net, torch.device('cpu'), precision)
+        _weights[key] = UNet3DWeights(sd, df.diffusion_net, torch.device(dev), precision)
     return _weights[key]
 
 
 def emit_step(width=32, ctx=64, O=6, concat=False, mp=True, precision='fp16', lo=0, hi=None, shard_block=None, deterministic=False,
-              up_fold=True, force_exchange=False, use_lanes=False, switch=None, gn_rg=1, **step_kw):
-    """samplers.emit_shape_step, as ShapeDenoiser._build_state calls it, on a CPU Builder -> (Builder, roots, its result)"""
+              up_fold=True, force_exchange=False, use_lanes=False, switch=None, gn_rg=1, dev='cpu', fill=None, **step_kw):
+    """samplers.emit_shape_step, as ShapeDenoiser._build_state calls it, on a CPU Builder -> (Builder, roots, its result).
+    ``dev`` / ``fill``: another device, and fill(name, *shape) for the contents of the host tables instead of zeros (the GPU witness,
+    tests/test_hip_plan_footprint.py: the recorded streams do not depend on either)"""
     from echoscene_amd import synth, hip, plan_vol
     from echoscene_amd.plan import GraphIndex
     from echoscene_amd.samplers import _cap, emit_shape_step, CANON_OBJECTS
-    dev = torch.device('cpu')
-    w = unet_weights(width, ctx, concat, mp, precision)
+    dev = torch.device(dev)
+    mk = (lambda name, *shape: torch.zeros(*shape)) if fill is None else fill
+    w = unet_weights(width, ctx, concat, mp, precision, dev)
     hi = O if hi is None else hi
     S, V0 = 4, 16 * 16 * 16
     ucw = V0 if concat else ctx
@@ -210,18 +214,18 @@ def emit_step(width=32, ctx=64, O=6, concat=False, mp=True, precision='fp16', lo
     g = GraphIndex(triples, O, dev, capacity=_cap(triples.shape[0]))
     b = make_builder(dev, precision=precision, o_hint=-CANON_OBJECTS if deterministic else 0, up_fold=up_fold and not deterministic,
                      shard_block=(hi - lo) if shard_block is None else shard_block, force_exchange=force_exchange, use_lanes=use_lanes)
-    tables = dict(emb=None, emb_all=torch.zeros(S, w.emb_all.N), t_lin=torch.zeros(S, 64) if w.enable_t_emb else None)
-    temb, coef, keep_tab = torch.zeros(S, w.mc), torch.zeros(S, 5 if step_kw.get('step_noise') else 4), torch.zeros(S, 2)
+    tables = dict(emb=None, emb_all=mk('emb_all', S, w.emb_all.N), t_lin=mk('t_lin', S, 64) if w.enable_t_emb else None)
+    temb, coef, keep_tab = mk('temb', S, w.mc), mk('coef', S, 5 if step_kw.get('step_noise') else 4), mk('keep_tab', S, 2)
     c = None
     if concat or not mp:
-        c = torch.zeros(O, V0 if concat else ctx)[lo:hi]
+        c = mk('c', O, V0 if concat else ctx)[lo:hi]
     world = O // (hi - lo)
     was = getattr(plan_vol, switch[0]) if switch else None
     try:
         if switch:
             setattr(plan_vol, switch[0], switch[1])
         hip.check(hip.lib().es_vol_set_option(b'gn_rg', gn_rg), 'es_vol_set_option')
-        out = emit_shape_step(b, w, g, torch.zeros(O, ucw), temb, tables, coef, keep_tab, S, (3, 16, 16, 16), lo, hi, c_local=c,
+        out = emit_shape_step(b, w, g, mk('uc', O, ucw), temb, tables, coef, keep_tab, S, (3, 16, 16, 16), lo, hi, c_local=c,
                               gather_rows=(hi - lo) * world, **step_kw)
     finally:
         if switch:
@@ -230,13 +234,13 @@ def emit_step(width=32, ctx=64, O=6, concat=False, mp=True, precision='fp16', lo
     return b, [w, g, tables, temb, coef, keep_tab], out
 
 
-def emit_vq(which):
+def emit_vq(which, dev='cpu', Oc=2):
     """emit_vq_decode / emit_vq_encode at a chunk of 2 objects with their default dims, as VQDecoder._plan / VQEncoder._plan call them"""
     from echoscene_amd import synth, config as escfg
     from echoscene_amd.model.vqvae import VQVAE
     from echoscene_amd.plan_vol import VQWeights, VQEncWeights, emit_vq_decode, emit_vq_encode
     from echoscene_amd.samplers import _cpu_sd
-    dev, Oc = torch.device('cpu'), 2
+    dev = torch.device(dev)
     if 'vq' not in _weights:
         p = escfg.vqvae_conf().model.params
         vq = VQVAE(dict(p.ddconfig), 64, p.embed_dim)

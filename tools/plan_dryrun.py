@@ -13,13 +13,16 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def emit_layout_step_cpu(mc=128, O=8, enable_t_emb=True, concat=False, seed=3):
-    """the denoiser of the layout loop step (samplers.emit_layout_step without the update, eps as a plain tensor) on a CPU Builder"""
+def emit_layout_step_cpu(mc=128, O=8, enable_t_emb=True, concat=False, seed=3, dev='cpu', fill=None):
+    """the denoiser of the layout loop step (samplers.emit_layout_step without the update, eps as a plain tensor) on a CPU Builder.
+    ``dev`` / ``fill``: another device, and fill(name, *shape) -> tensor on it for the per-step tables instead of zeros (the GPU
+    witness of tests/test_hip_plan_footprint.py)"""
     from echoscene_amd import synth, config as escfg
     from echoscene_amd.model.unet import UNet1DModel
     from echoscene_amd.plan import Builder, GraphIndex, UNet1DWeights
     from echoscene_amd.samplers import _cap, _cpu_sd, emit_layout_step
-    dev = torch.device('cpu')
+    dev = torch.device(dev)
+    mk = (lambda name, *shape: torch.zeros(*shape, device=dev)) if fill is None else fill
     net = UNet1DModel(**escfg.layout_denoiser_kwargs(mc, enable_t_emb=enable_t_emb, concat=concat))
     synth.seeded_fill_(net, prefix='dry.')
     w = UNet1DWeights(_cpu_sd(net), net, dev)
@@ -28,9 +31,9 @@ def emit_layout_step_cpu(mc=128, O=8, enable_t_emb=True, concat=False, seed=3):
     b = Builder(dev)
     eps = b.buf(O, net.out_channels)
     n_steps = 4
-    tables = dict(emb=None, emb_all=torch.zeros(n_steps, w.emb_all.N), t_lin=torch.zeros(n_steps, 64) if enable_t_emb else None)
-    bufs = emit_layout_step(b, w, g, torch.randn(O, 640), torch.zeros(n_steps, mc), tables, n_steps, eps_out=eps)
-    return b, dict(x=bufs['x'], eps=eps, step=bufs['step'])
+    tables = dict(emb=None, emb_all=mk('emb_all', n_steps, w.emb_all.N), t_lin=mk('t_lin', n_steps, 64) if enable_t_emb else None)
+    bufs = emit_layout_step(b, w, g, torch.randn(O, 640), mk('temb', n_steps, mc), tables, n_steps, eps_out=eps)
+    return b, dict(x=bufs['x'], eps=eps, step=bufs['step'], objbuf=bufs['objbuf'], oe_w=bufs['oe_w'])
 
 
 def emit_shape_step_cpu(O=32, width=224, precision='fp16', up_fold=True, deterministic=False, seed=100, weights=None):
